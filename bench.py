@@ -24,16 +24,26 @@ merge contexts.  Every step still counts one full batch into its own sorted
 table.  The line's `value` is this configs[1] workload at every N (weak
 scaling: the driver's per-N values compare like for like).
 
-After it, the same invocation measures BASELINE configs[2] (C3: 25.17 Gbases
-from a 1 Gbp genome, sharded 1/N over the ranks, strong scaling, c3_run) and
-reports it in the same line as `c3` (`--c3-steps 0` skips it; `--workload c3`
-makes C3 the line's `value`).
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the
+headline figure needs: it sets up, warms up, times the K steps, writes the
+last step's table if `--dump-outputs DIR` is given, and prints ONE JSON line on
+rank 0 (the driver's contract) with `value` and `ms_per_step`.
 
-Prints ONE JSON line on rank 0 (the driver's contract), including `roofline`
-for the dominant kernel (HIP events on the engine's own stream, from a
-single-stream pass of the same K steps after the timed region) and
-`cpu_baseline` (the oracle, oracle/okm_oracle.c, on a bounded sample, rank 0
-at N=1 only).
+`--full` adds everything else the line can carry, each from a pass of its own
+after the timed region: `with_dense_table` and `single_job` (the same K steps
+with the dense arrays gathered / on one stream), `kernels` and `roofline` for
+the dominant kernel (HIP events on the engine's own stream, from a
+single-stream pass of the same K steps), `cpu_baseline` / `cpu_baseline_mt`
+(the oracle, oracle/okm_oracle.c, on a bounded sample, rank 0 at N=1 only),
+and BASELINE configs[2] (C3: 25.17 Gbases from a 1 Gbp genome, sharded 1/N
+over the ranks, strong scaling, c3_run) reported in the same line as `c3`
+(`--c3-steps 0` skips it; `--workload c3` makes C3 the line's `value`).
+Without `--full` those fields are null (`kernels` empty, no `c3`).
+
+`--dump-outputs DIR` writes what the last timed step computed, the sorted
+(key, count) table a caller of the path receives (okm_result_device), as
+float64 .npy files: see dump_table.  The inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 
 from __future__ import annotations
@@ -161,12 +171,64 @@ def emit(out):
     os.write(_STDOUT_FD, (json.dumps(out) + "\n").encode())
 
 
+DUMP_BLOCK = 4096    # table entries per sampled block
+DUMP_BLOCKS = 512    # blocks: 2,097,152 entries x 3 float64 arrays = 50.3 MB
+DUMP_SEED = 1
+
+
+def dump_table(dirpath, ctr, kmers, rank, world):
+    """--dump-outputs: the sorted (key, count) table `ctr` holds, as a caller
+    receives it (okm_result_device: dense key / count arrays on the device),
+    written as float64 arrays, every value exact:
+
+      keys_hi32.npy, keys_lo32.npy   key >> 32 and key & 0xffffffff
+      counts.npy                     the keys' counts
+      summary.npy                    [distinct keys (the table's length),
+                                      k-mer instances counted (`kmers`)]
+
+    A table of at most DUMP_BLOCKS * DUMP_BLOCK entries is written whole; of a
+    larger one, DUMP_BLOCKS blocks of DUMP_BLOCK consecutive entries in table
+    order: the first, the last and seeded (DUMP_SEED) starts between them, the
+    same for every table of one length.  At N>1 each rank writes its owned
+    key range, the names suffixed `_rank<r>`."""
+    d_keys, d_counts, n = ctr.result_device()
+    ctr.synchronize()
+    if n <= DUMP_BLOCKS * DUMP_BLOCK:
+        starts, blk = [0], n
+    else:
+        blk = DUMP_BLOCK
+        rng = np.random.default_rng(DUMP_SEED)
+        starts = np.sort(np.concatenate([[0, n - blk], rng.integers(0, n - blk + 1, DUMP_BLOCKS - 2)]))
+    keys = np.empty(len(starts) * blk, np.uint64)
+    counts = np.empty(len(starts) * blk, np.uint64)
+    for i, s in enumerate(starts):  # [s, s + blk) lies inside [0, n)
+        for d_src, dst in ((d_keys, keys), (d_counts, counts)):
+            part = dst[i * blk:(i + 1) * blk]
+            if part.nbytes:
+                _lib.check(okm.lib().okm_memcpy_d2h(part.ctypes.data, d_src + 8 * int(s), part.nbytes),
+                           "okm_memcpy_d2h")
+    os.makedirs(dirpath, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    arrays = {"keys_hi32": keys >> np.uint64(32), "keys_lo32": keys & np.uint64(0xFFFFFFFF), "counts": counts,
+              "summary": np.array([n, kmers])}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, f"{name}{sfx}.npy"), a.astype(np.float64))
+    log(f"[rank {rank}] --dump-outputs: {len(keys)} of {n} table entries -> {dirpath}")
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reads", type=int, default=READS_PER_GPU, help="reads per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the line reports beside its headline figure: "
+                         "dense-table and single-job passes, per-kernel timing and roofline, CPU baselines, C3 "
+                         "(the options below that tune those apply only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's sorted (key, count) table to DIR as float64 .npy files "
+                         "(whole if small, else a fixed seeded sample of it)")
     ap.add_argument("--cpu-sample-reads", type=int, default=300_000,
                     help="reads in the bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--cpu-mt-reads", type=int, default=800_000,
@@ -272,6 +334,7 @@ def main():
     else:
         ctrs, mergers = [okm.KmerCounter(K, "count", device) for _ in range(S)], []
     ctr = ctrs[0]
+    last_ctx = [ctr]  # the context that counted the last step of run_steps (N=1)
 
     def run_steps(nsteps, dense=False):
         """nsteps batches through the path; returns the distinct count (N=1)
@@ -294,6 +357,8 @@ def main():
                         if nxt[0] >= nsteps:
                             return
                         nxt[0] += 1
+                        if nxt[0] == nsteps:
+                            last_ctx[0] = c
                     res.append(count_batch(c, dense))
             except BaseException as e:  # surfaced below
                 err.append(e)
@@ -329,12 +394,18 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    # --dump-outputs: the last timed step's table (N>1: this rank's owned range
+    # of the last merge), before any later pass counts into the contexts again
+    if args.dump_outputs:
+        dump_table(args.dump_outputs, pipe.owned() if dist_on else last_ctx[0], ctr.engine_info()["kmers"],
+                   rank, world)
+    # Everything below the timed region is --full's: passes of their own.
     # The step ends with the sorted table as per-item runs (the dense arrays
     # are gathered by their first reader).  The same K steps again, each also
     # gathering the dense (keys, counts) arrays: the conservative rate, for a
     # caller that wants the flat table every batch.
     dense_ms = None
-    if not dist_on:
+    if args.full and not dist_on:
         barrier_sync()
         t2 = time.perf_counter()
         run_steps(args.steps, dense=True)
@@ -343,7 +414,7 @@ def main():
     # one job alone (one context, one stream, one host thread): the latency of
     # a single batch, beside the throughput of S batches in flight above
     single_ms = None
-    if not dist_on and S > 1:
+    if args.full and not dist_on and S > 1:
         barrier_sync()
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -359,7 +430,7 @@ def main():
     # so `kernels` carries that gather's cost (compact_items) beside the
     # count's kernels.
     stats = {}
-    if not args.no_timing:
+    if args.full and not args.no_timing:
         ctr.set_timing(True)
         for i in range(args.steps):
             count_batch(ctr)
@@ -372,14 +443,15 @@ def main():
     # ---- CPU baseline: the oracle on a bounded sample (rank 0, N=1) -------
     # plus SURVEY §8(d)'s labelled multi-threaded restatement beside it
     cpu = cpu_mt = None
-    if rank == 0 and world == 1 and args.cpu_sample_reads > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample_reads > 0:
         cpu, cpu_mt = cpu_baselines(batch, min(args.cpu_sample_reads, args.reads),
                                     min(args.cpu_mt_reads, args.reads), device, "the same batch")
 
     # BASELINE configs[2] (C3) in the same invocation, every rank (its merge is
     # collective): the C2 contexts go first so the C3 shard has the device
     c3 = None
-    if args.c3_steps > 0:
+    run_c3 = args.full and args.c3_steps > 0
+    if run_c3:
         for c in ctrs + mergers:
             c.close()
         dbuf.free()
@@ -466,7 +538,7 @@ def main():
         comm.close()
     if dist_on:
         dist.destroy_process_group()
-    if args.c3_steps <= 0:
+    if not run_c3:
         dbuf.free()
 
 
@@ -483,7 +555,8 @@ def main_c3(args):
     world, rank, device = rank_device(args)
     dist_on = world > 1 or os.environ.get("OKM_BENCH_EXCHANGE") == "1"
     comm = init_comm(world, rank, device) if dist_on else None
-    out = c3_run(args, world, rank, device, comm, dist_on, args.steps, args.warmup, baselines=True)
+    out = c3_run(args, world, rank, device, comm, dist_on, args.steps, args.warmup, baselines=True,
+                 dump_dir=args.dump_outputs)
     if out is not None:
         emit(out)
     if comm is not None:
@@ -492,10 +565,11 @@ def main_c3(args):
         dist.destroy_process_group()
 
 
-def c3_run(args, world, rank, device, comm, dist_on, steps, warmup, baselines):
+def c3_run(args, world, rank, device, comm, dist_on, steps, warmup, baselines, dump_dir=None):
     """Time `steps` whole C3 jobs (after `warmup` untimed ones) on every rank
     and return rank 0's line (None on the other ranks).  Every rank must call
-    it (the merge is collective); it releases its contexts and shard buffer."""
+    it (the merge is collective); it releases its contexts and shard buffer.
+    dump_dir: --dump-outputs, the last timed job's table (dump_table)."""
     total = args.c3_reads
     r0, r1 = total * rank // world, total * (rank + 1) // world
     nreads = r1 - r0
@@ -575,6 +649,8 @@ def c3_run(args, world, rank, device, comm, dist_on, steps, warmup, baselines):
     barrier_sync()
     dt = time.perf_counter() - t_start
     info = ctr.engine_info()
+    if dump_dir:
+        dump_table(dump_dir, ctr, info["kmers"], rank, world)
     distinct_global = n_last
     if dist_on:
         dev_t = "cpu"
@@ -586,7 +662,7 @@ def c3_run(args, world, rank, device, comm, dist_on, steps, warmup, baselines):
         distinct_global = int(nd.item())
     # per-kernel HIP-event timing of the local count: one more step, single stream
     stats = {}
-    if not args.no_timing:
+    if args.full and not args.no_timing:
         ctr.set_timing(True)
         ctr.reset()
         for off, nb in batches:
@@ -596,7 +672,7 @@ def c3_run(args, world, rank, device, comm, dist_on, steps, warmup, baselines):
         ctr.set_timing(False)
 
     cpu = cpu_mt = None
-    if baselines and rank == 0 and world == 1 and args.cpu_sample_reads > 0:
+    if args.full and baselines and rank == 0 and world == 1 and args.cpu_sample_reads > 0:
         m = min(args.cpu_sample_reads, nreads)
         mm = min(max(m, args.cpu_mt_reads), nreads)
         host = np.empty(mm * stride, dtype=np.uint8)

@@ -4,7 +4,7 @@
 (one per GPU) or fail loudly, never report one GPU as N (BASELINE metric "at
 1/2/4/8 MI355X").  These tests drive the launcher with a
 stub rank (tests/launch_stub.py) that stops before any GPU call, and
-bench.py itself on this GPU-less container, where asking for 2 ranks must
+bench.py itself with no GPU visible to it, where asking for 2 ranks must
 fail within seconds.
 """
 
@@ -117,9 +117,10 @@ def test_more_ranks_than_devices_is_an_error(monkeypatch, capsys):
 
 
 def test_bench_gpus_2_without_devices_fails_fast():
-    """This container has no GPU: bench.py --gpus 2 must exit non-zero with
-    the rank/device message within seconds, having started no rank."""
-    env = dict(os.environ)
+    """With no GPU visible (none in the machine, or every device hidden from
+    the child by HIP_VISIBLE_DEVICES=-1) bench.py --gpus 2 must exit non-zero
+    with the rank/device message within seconds, having started no rank."""
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1")
     env.pop("WORLD_SIZE", None)
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"],

@@ -8,7 +8,7 @@ reps=$1; shift
 for r in $(seq 1 "$reps"); do
   for n in "$@"; do
     if [ "$n" = main ]; then lib=orion-kmer_amd/build/liborion_kmer.so; else lib=orion-kmer_amd/build_$n/liborion_kmer.so; fi
-    OKM_LIB=$lib timeout -k 10 300 python bench.py --workload c3 --c3-reads 20971520 --steps 3 --warmup 1 \
+    OKM_LIB=$lib timeout -k 10 300 python bench.py --full --workload c3 --c3-reads 20971520 --steps 3 --warmup 1 \
       --cpu-sample-reads 0 > gpurun_out/abc3/${n}_$r.json 2> gpurun_out/abc3/${n}_$r.err || exit 1
   done
 done

@@ -8,7 +8,7 @@ reps=$1; shift
 for r in $(seq 1 "$reps"); do
   for n in "$@"; do
     if [ "$n" = main ]; then lib=orion-kmer_amd/build/liborion_kmer.so; else lib=orion-kmer_amd/build_$n/liborion_kmer.so; fi
-    OKM_LIB=$lib timeout -k 10 300 python -u bench.py --workload c3 --steps 2 --warmup 1 --cpu-sample-reads 0 \
+    OKM_LIB=$lib timeout -k 10 300 python -u bench.py --full --workload c3 --steps 2 --warmup 1 --cpu-sample-reads 0 \
       --cpu-mt-reads 0 > gpurun_out/abc3f/${n}_$r.json 2> gpurun_out/abc3f/${n}_$r.err || { echo "$n failed"; tail -5 gpurun_out/abc3f/${n}_$r.err; exit 1; }
     echo "$n rep $r done"
   done

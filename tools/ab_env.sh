@@ -12,7 +12,7 @@ for r in $(seq 1 "$reps"); do
   for spec in "$@"; do
     n=${spec%%=*}; envs=${spec#*=}
     [ "$r" = 1 ] && names+=("$n")
-    env $envs timeout -k 10 300 python bench.py --steps 10 --warmup 2 --cpu-sample-reads 0 --cpu-mt-reads 0 \
+    env $envs timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --cpu-sample-reads 0 --cpu-mt-reads 0 \
       ${AB_BENCH_ARGS:---c3-steps 0} > gpurun_out/abe/${n}_$r.json 2> gpurun_out/abe/${n}_$r.err || exit 1
   done
 done

@@ -4,7 +4,7 @@
 # which first take and release a large device block (run on the GPU box).
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 mkdir -p gpurun_out/mode
-ARGS="--steps 3 --warmup 1 --cpu-sample-reads 0 --cpu-mt-reads 0 --c3-steps 0"
+ARGS="--full --steps 3 --warmup 1 --cpu-sample-reads 0 --cpu-mt-reads 0 --c3-steps 0"
 for i in 1 2 3; do
   for pre in 0 96; do
     timeout -k 10 200 python -u -c "

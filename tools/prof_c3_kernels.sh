@@ -3,7 +3,7 @@
 # bench.py --workload c3 at P=1 (whole job) and at a P=2 shard's size.
 mkdir -p gpurun_out
 for reads in 167772160 83886080; do
-  timeout -k 10 300 python bench.py --workload c3 --c3-reads $reads --steps 1 --warmup 1 --cpu-sample-reads 0 \
+  timeout -k 10 300 python bench.py --full --workload c3 --c3-reads $reads --steps 1 --warmup 1 --cpu-sample-reads 0 \
       > gpurun_out/r03_c3prof_$reads.json 2> gpurun_out/r03_c3prof_$reads.err || exit $?
   python - $reads <<'PY'
 import json, sys
