@@ -380,7 +380,7 @@ typedef struct okm_engine_info {
     uint64_t device_peak_bytes;  /* high-water mark of live device allocations since okm_create / okm_reset */
     uint64_t host_bytes;     /* sorted tables this context keeps in host memory (moved off a full device) */
     uint32_t spills;         /* tables moved to host memory since okm_create / okm_reset */
-    uint32_t pad;
+    uint32_t l1_blocks;      /* workgroups of the last extraction launch (each walks n / l1_blocks bytes, in whole tiles) */
 } okm_engine_info;
 okm_status okm_engine_info_get(okm_ctx *ctx, okm_engine_info *info);
 

@@ -61,7 +61,12 @@ typedef enum okm_test_knob {
      * own L1 run when memory-bounded counting splits them (the default);
      * 1 also with group_keys' forced groups, 0 never */
     OKM_TEST_GROUP_OVER = 16,
-    OKM_TEST_KNOBS = 17
+    /* extraction: at most this many workgroups per batch instead of 8192, so
+     * that a batch of a few tiles walks the scatter kernels' tile loop more
+     * than once (okm_engine.hip l1_batch; okm_engine_info.l1_blocks reports
+     * the workgroups launched) */
+    OKM_TEST_L1_MAX_BLOCKS = 17,
+    OKM_TEST_KNOBS = 18
 } okm_test_knob;
 
 /* value < 0 unsets the knob (the product default). */

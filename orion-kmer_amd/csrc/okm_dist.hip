@@ -1076,15 +1076,20 @@ okm_status merge_owned_n(okm_ctx *const *locals, okm_comm *m, okm_ctx *const *ow
         // one rank: the owner's range is the whole key space and its only
         // slice the local table -- handed over, no exchange and no copy
         // (adopt_result; owner == local, or a local still holding runs, takes
-        // the general path below)
+        // the general path below).  All tables or none: an adoption resets
+        // the local, which the general path would then read empty, so every
+        // pair is asked (can_adopt_result) before any is adopted.
         bool all = true;
-        for (int i = 0; i < nt && all; ++i) {
-            bool adopted = false;
-            OKM_TRY(adopt_result(owners[i], locals[i], &adopted));
-            if (adopted && n_owned) OKM_TRY(okm_count(owners[i], n_owned + i));  // (counted: returns its size)
-            all = adopted;
-        }
+        for (int i = 0; i < nt && all; ++i)  // (an owner that is another table's context would be reset under it)
+            for (int j = 0; j < nt && all; ++j) all = i == j || (owners[i] != owners[j] && owners[i] != locals[j]);
+        for (int i = 0; i < nt && all; ++i) OKM_TRY(can_adopt_result(owners[i], locals[i], &all));
         if (all) {
+            for (int i = 0; i < nt; ++i) {
+                bool adopted = false;
+                OKM_TRY(adopt_result(owners[i], locals[i], &adopted));
+                if (!adopted) return fail(OKM_E_STATE, "okm_merge_owned_n: a table checked as adoptable was not adopted");
+                if (n_owned) OKM_TRY(okm_count(owners[i], n_owned + i));  // (counted: returns its size)
+            }
             m->last_ms[0] = m->last_ms[1] = m->last_ms[2] = 0;
             m->last_ms[3] = ms_since(t0);
             m->last_bytes[0] = m->last_bytes[1] = 0;

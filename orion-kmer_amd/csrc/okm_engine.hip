@@ -1151,10 +1151,13 @@ static okm_status l1_batch(okm_ctx *c, const uint8_t *d_seq, uint64_t n) {
     uint64_t tiles = (n + tile - 1) / tile;
     // extraction workgroups: 8192 (C2: ~4 tiles each) against 2048: extract_scatter
     // 1.438 vs 1.484 ms over 4 interleaved runs, 4096 1.447 (profiles/r04_ab_extract_blocks.txt)
-    constexpr uint64_t max_blocks = 8192;
+    uint64_t max_blocks = 8192;
+    if (const int64_t e = test_knob(OKM_TEST_L1_MAX_BLOCKS); e > 0)  // tests: several tiles per workgroup
+        max_blocks = (uint64_t)e;
     uint32_t nblocks = (uint32_t)std::min<uint64_t>(tiles, max_blocks);
     uint64_t chunk = ((tiles + nblocks - 1) / nblocks) * tile;
     nblocks = (uint32_t)((n + chunk - 1) / chunk);
+    c->info.l1_blocks = nblocks;
     ExtractGeom g{n, c->k, c->shift1, c->nbins, nblocks, chunk, 1};
     const uint32_t S = kL1SampleStride;
     if (S > 1 && tiles >= 64ull * S && c->nbins > 1) {
@@ -3024,14 +3027,26 @@ namespace okm {
 // that device -- so the table stays where it is and is later returned to
 // the pool that holds it; the local context is left reset (its input runs
 // are released first); *adopted says whether it happened.
-okm_status adopt_result(okm_ctx *owner, okm_ctx *local, bool *adopted) {
-    *adopted = false;
+// Would adopt_result(owner, local) adopt?  Its early returns, in its order:
+// the local is counted here (it is counted by either merge path anyway), so
+// that input_lost is known.  Nothing else changes: okm_merge_owned_n asks this
+// of every table before it adopts any, because an adoption resets the local
+// and the general path can no longer read it.
+okm_status can_adopt_result(okm_ctx *owner, okm_ctx *local, bool *adoptable) {
+    *adoptable = false;
     if (owner == local || owner->device != local->device || owner->k != local->k || owner->mode != local->mode ||
         owner->wide != local->wide)
         return OKM_OK;
     HIP_TRY(hipSetDevice(local->device));
     OKM_TRY(do_count(local));
-    if (local->input_lost) return OKM_OK;
+    *adoptable = !local->input_lost;
+    return OKM_OK;
+}
+
+okm_status adopt_result(okm_ctx *owner, okm_ctx *local, bool *adopted) {
+    OKM_TRY(can_adopt_result(owner, local, adopted));
+    if (!*adopted) return OKM_OK;
+    *adopted = false;
     OKM_TRY(okm_reset(owner));  // (synchronises the owner's stream)
     OKM_TRY(sync(local));
     // the counted input is no longer needed (the local is left reset, and no

@@ -43,6 +43,9 @@ okm_status result_view(okm_ctx *c, const uint64_t **keys, const uint64_t **count
 // okm_merge_owned at one rank: the owner takes the local context's table
 // without a copy (the two swap device pools); the local is left reset.
 okm_status adopt_result(okm_ctx *owner, okm_ctx *local, bool *adopted);
+// Whether adopt_result would adopt (counts the local; changes nothing else):
+// okm_merge_owned_n adopts every table or none.
+okm_status can_adopt_result(okm_ctx *owner, okm_ctx *local, bool *adoptable);
 
 // Context accessors for the other translation units (okm_probe.hip).
 int ctx_device(const okm_ctx *c);

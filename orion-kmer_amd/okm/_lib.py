@@ -63,7 +63,7 @@ class EngineInfo(Structure):
                 ("l2_bits", c_uint32), ("levels", c_uint32), ("work_items", c_uint32),
                 ("max_partition", c_uint64), ("device_bytes", c_uint64), ("groups", c_uint32),
                 ("folds", c_uint32), ("device_peak_bytes", c_uint64), ("host_bytes", c_uint64),
-                ("spills", c_uint32), ("pad", c_uint32)]
+                ("spills", c_uint32), ("l1_blocks", c_uint32)]
 
 
 class Key128(Structure):

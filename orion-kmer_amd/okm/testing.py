@@ -28,6 +28,7 @@ KNOBS: Dict[str, int] = {
     "no_libdeflate": 14,
     "hbm_budget_bytes": 15,
     "group_over": 16,
+    "l1_max_blocks": 17,
 }
 
 

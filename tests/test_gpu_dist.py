@@ -191,6 +191,115 @@ def test_merge_owned_into_local_context(comm1):
     assert np.array_equal(gk, ek) and np.array_equal(gc, ec)
 
 
+@pytest.fixture(params=["rccl", "loopback"])
+def one_rank(request, comm1):
+    """A one-rank communicator of either transport."""
+    if request.param == "rccl":
+        yield comm1
+        return
+    (c,) = okm.Comm.init_loopback(1)
+    assert c.rank == 0 and c.size == 1
+    yield c
+    c.close()
+
+
+class _TwoTables:
+    """Two counted tables A and B (20 k reads each over one genome, so they
+    share keys; a hot key takes counts past the one-byte escape), their fresh
+    owners and the oracle's tables."""
+
+    def __init__(self, k, mode="count", wide=False):
+        from oracle import OracleCounterWide
+        self.ctxs, self.want = [], []
+        buf = None
+        try:
+            for seed in (21, 22):
+                b = okm.synth_reads(20_000, 150, genome_len=300_000, genome_seed=20, seed=seed)
+                b.reshape(20_000, 151)[::50, :150] = ord("A") if seed == 21 else ord("C")
+                ref = OracleCounterWide(k) if wide else OracleCounter(k)
+                ref.add_separated(b)
+                ek, ec = ref.result(1)
+                assert (ec > 255).any()
+                if mode == "set":
+                    ec = np.ones_like(ec)
+                self.want.append((ek, ec))
+                buf = buf or okm.DeviceBuffer(len(b))
+                buf.upload(b)
+                local = self._new(k, mode, wide)
+                local.add_device_batch(buf.address, len(b))
+                assert local.count() == len(ek)
+            self.a, self.b = self.ctxs
+            self.oa, self.ob = self._new(k, mode, wide), self._new(k, mode, wide)
+        except BaseException:
+            self.close()
+            raise
+        finally:
+            if buf:
+                buf.free()
+
+    def _new(self, k, mode, wide):
+        c = okm.KmerCounter(k, mode, wide=wide)
+        self.ctxs.append(c)
+        return c
+
+    def close(self):
+        for c in self.ctxs:
+            c.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def check(self, sizes, locals_, owners, set_mode=False):
+        """Every owner holds exactly its table, the sizes are the tables', and
+        every local holds nothing or exactly its own table."""
+        assert list(sizes) == [len(self.want[0][0]), len(self.want[1][0])]
+        for i, (local, owner) in enumerate(zip(locals_, owners)):
+            ek, ec = self.want[i]
+            gk, gc = owner.result(1)
+            assert np.array_equal(gk.reshape(ek.shape), ek), i
+            if not set_mode:
+                assert np.array_equal(gc, ec), i
+            assert local.count() in (0, len(ek)), i
+
+
+def _adoption_case(t, which):
+    return {"first": ([t.a, t.b], [t.oa, t.b]),     # table 0 adoptable, table 1 owner == local
+            "second": ([t.a, t.b], [t.a, t.ob]),    # the mirror image
+            "both": ([t.a, t.b], [t.oa, t.ob])}[which]
+
+
+@pytest.mark.parametrize("which", ["first", "second", "both"])
+def test_merge_owned_n_one_rank_adoption(one_rank, which):
+    """okm_merge_owned_n at one rank adopts every table or none.  With table 0
+    adoptable and table 1 not ("first"), adopting table by table reset the
+    local of table 0 before the general path read it: its counts were lost
+    and n_owned[0] overwritten."""
+    with _TwoTables(31) as t:
+        locals_, owners = _adoption_case(t, which)
+        sizes = one_rank.merge_owned_n(locals_, owners)
+        t.check(sizes, locals_, owners)
+
+
+def test_merge_owned_n_one_rank_adoption_wide(one_rank):
+    with _TwoTables(45, wide=True) as t:
+        locals_, owners = _adoption_case(t, "first")
+        sizes = one_rank.merge_owned_n(locals_, owners)
+        t.check(sizes, locals_, owners)
+
+
+def test_distributed_compare_one_rank_mixed_adoption(one_rank):
+    with _TwoTables(21, mode="set") as t:
+        (ka, _), (kb, _) = t.want
+        got = okm.distributed_compare(one_rank, t.a, t.b, t.oa, t.b)
+        inter = len(np.intersect1d(ka, kb, assume_unique=True))
+        assert 0 < inter < min(len(ka), len(kb))
+        assert got == (len(ka), len(kb), inter)
+        t.check(got[:2], [t.a, t.b], [t.oa, t.b], set_mode=True)
+
+
 def _group_count(k, batches, n_gpus, min_count=1):
     lib = okm._lib.load()
     g = ctypes.c_void_p()
