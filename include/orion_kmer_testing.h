@@ -66,13 +66,25 @@ typedef enum okm_test_knob {
      * than once (okm_engine.hip l1_batch; okm_engine_info.l1_blocks reports
      * the workgroups launched) */
     OKM_TEST_L1_MAX_BLOCKS = 17,
-    OKM_TEST_KNOBS = 18
+    /* n > 0: every allocation from a context's device arena (okm_engine.hip
+     * DevPool::get) decrements it, and the one that brings it to 0 fails with
+     * OKM_E_NOMEM before anything is taken or mapped and leaves the knob
+     * unset -- the out-of-memory recovery and every error path's block
+     * bookkeeping, one allocation at a time.  A clean run under a huge n
+     * tells how many allocations it made. */
+    OKM_TEST_FAIL_ALLOC = 18,
+    OKM_TEST_KNOBS = 19
 } okm_test_knob;
 
 /* value < 0 unsets the knob (the product default). */
 void okm_test_set(okm_test_knob knob, int64_t value);
 /* The knob's value, -1 when unset. */
 int64_t okm_test_get(okm_test_knob knob);
+/* Bytes of the context's device arena that are allocated right now: 0 after
+ * okm_reset, since only runs, the result and its pending state live there
+ * between calls. */
+struct okm_ctx;
+uint64_t okm_test_device_in_use(struct okm_ctx *c);
 
 #ifdef __cplusplus
 }

@@ -148,6 +148,8 @@ struct DevPool {
     // the other pools on the device) are unmapped first -- after a device
     // sync, since a freed range's last kernel may still be in flight.
     okm_status get(size_t bytes, void **out) {
+        if (test_fail_alloc())
+            return fail(OKM_E_NOMEM, "device arena: allocation failed by the test hook OKM_TEST_FAIL_ALLOC");
         std::lock_guard<std::mutex> lk(mu);
         if (!init_locked()) return fail(OKM_E_DEVICE, "device arena: no virtual memory management on this device");
         bytes = VmmArena::round_up(std::max<size_t>(bytes, 256), 256);
@@ -296,6 +298,57 @@ static okm_status pool_get(DevPool &pool, size_t n, T **out) {
     *out = static_cast<T *>(p);
     return OKM_OK;
 }
+
+// The arena blocks one step of a count holds: whatever is still here when the
+// scope ends -- an early return on an error -- goes back to the pool, so a
+// failed step strands nothing beside the caller's retry.  A successful path
+// frees at its own explicit points (free_all / put / move_to: the memory plan
+// depends on when a block comes back), never by running off the end.
+// A block has exactly ONE owner at any time: a Blocks, a run (free_run), the
+// result (invalidate_result) or Pending::hold.  DevPool::put ignores an offset
+// that is not live, but a second put after the range was taken again would
+// free somebody else's block; single ownership is what rules that out, so a
+// block that changes hands is disowned here as it is handed over.  Only
+// allocation bases are owned, never a pointer into a block (a table's counts
+// behind its keys).  Holds the DevPool, not the context: adopt_result swaps
+// the contexts' pools, and the blocks belong to the pool.
+class Blocks {
+public:
+    explicit Blocks(DevPool &pool) : pool_(&pool) {}
+    Blocks(const Blocks &) = delete;
+    Blocks &operator=(const Blocks &) = delete;
+    ~Blocks() { free_all(); }
+    template <typename T> okm_status get(size_t n, T **out) {
+        OKM_TRY(pool_get(*pool_, n, out));
+        held_.push_back(*out);
+        return OKM_OK;
+    }
+    // Take over a block of the pool (null, or a pointer into a block -- no allocation -- is not taken).
+    void own(void *p) {
+        if (p && pool_->size_of(p)) held_.push_back(p);
+    }
+    void disown(void *p) { held_.erase(std::remove(held_.begin(), held_.end(), p), held_.end()); }
+    // One block back to the pool now.
+    void put(void *p) {
+        const size_t n = held_.size();
+        disown(p);
+        if (held_.size() != n) pool_->put(p);
+    }
+    void move_to(std::vector<void *> &hold) {
+        hold.insert(hold.end(), held_.begin(), held_.end());
+        held_.clear();
+    }
+    void move_to(Blocks &other) { move_to(other.held_); }
+    void free_all() {
+        for (void *p : held_) pool_->put(p);
+        held_.clear();
+    }
+    const std::vector<void *> &held() const { return held_; }
+
+private:
+    DevPool *pool_;
+    std::vector<void *> held_;
+};
 
 static bool debug_sync() {
     static int v = -1;
@@ -603,6 +656,15 @@ static void host_table_free(okm_ctx *c, uint64_t *keys, uint64_t *counts, uint64
     c->host_bytes -= std::min(c->host_bytes, b);
 }
 
+// A failure once a count may have written into a run (on): the input is gone.
+struct Lost {
+    okm_ctx *c;
+    bool on = false;
+    ~Lost() {
+        if (on) c->input_lost = true;
+    }
+};
+
 static void drop_pending(okm_ctx *c) {
     for (void *p : c->pend.hold) c->pool->put(p);
     c->pend = okm_ctx::Pending{};
@@ -621,6 +683,15 @@ static void invalidate_result(okm_ctx *c) {
     c->n_res = 0;
     c->counted = false;
     c->res_is_input = false;
+}
+
+// Blocks for a result of n entries, taken straight into the context: the
+// result owns them at once, and a failure gives back what it had taken.
+static okm_status get_result(okm_ctx *c, uint64_t n) {
+    okm_status st = pool_get(*c->pool, std::max<uint64_t>(n, 1) * c->kw, &c->res_keys);
+    if (st == OKM_OK) st = pool_get(*c->pool, std::max<uint64_t>(n, 1), &c->res_counts);
+    if (st != OKM_OK) invalidate_result(c);
+    return st;
 }
 
 // Device memory this context may still use: the budget (OKM_HBM_CAP) less
@@ -654,12 +725,13 @@ static okm_status ensure_dense(okm_ctx *c) {
     const uint64_t nd = c->n_res;
     const uint64_t kb = std::max<uint64_t>(nd, 1) * 8 * c->kw, cb = std::max<uint64_t>(nd, 1) * 8;
     uint64_t *dk = nullptr, *dc = nullptr, *hk = nullptr, *hc = nullptr;
-    okm_status st = pool_get(*c->pool, kb / 8, &dk);
-    if (st == OKM_OK) st = pool_get(*c->pool, cb / 8, &dc);
+    Blocks dense(*c->pool);
+    okm_status st = dense.get(kb / 8, &dk);
+    if (st == OKM_OK) st = dense.get(cb / 8, &dc);
     if (st == OKM_E_NOMEM) {
         // no room on the device for the dense copy: the gather writes it
         // straight into page-locked, device-mapped host memory (the host tier)
-        c->pool->put(dk);
+        dense.free_all();
         dk = dc = nullptr;
         if (hipHostMalloc(reinterpret_cast<void **>(&hk), kb, hipHostMallocMapped) != hipSuccess ||
             hipHostMalloc(reinterpret_cast<void **>(&hc), cb, hipHostMallocMapped) != hipSuccess) {
@@ -682,23 +754,19 @@ static okm_status ensure_dense(okm_ctx *c) {
         st = hipGetLastError() == hipSuccess ? sync(c) : fail(OKM_E_DEVICE, "compact_items launch");
     }
     if (st != OKM_OK) {
-        if (hk) {
-            host_pinned_free(hk);
-            host_pinned_free(hc);
-        } else {
-            c->pool->put(dk);
-            c->pool->put(dc);
-        }
+        host_pinned_free(hk);
+        host_pinned_free(hc);
         return st;
     }
-    for (void *p : c->pend.hold) c->pool->put(p);
-    c->pend = okm_ctx::Pending{};
+    drop_pending(c);
     if (hk) {
         c->res_keys = hk;
         c->res_counts = hc;
         c->res_host = true;
         c->host_bytes += kb + cb;
     } else {
+        dense.disown(dk);  // published: the result owns both from here
+        dense.disown(dc);
         c->res_keys = dk;
         c->res_counts = dc;
     }
@@ -792,7 +860,8 @@ static okm_status l1_sampled(okm_ctx *c, const uint8_t *d_seq, uint64_t n, const
     launch_l1_capacity(c->stream, c->Hg, nb, scale, mul, align, limit, cur, c->l1cap);
     HIP_TRY(hipGetLastError());
     Run run;
-    OKM_TRY(pool_get(*c->pool, limit * c->kw, &run.keys));
+    Blocks own(*c->pool);
+    OKM_TRY(own.get(limit * c->kw, &run.keys));
     c->timer.begin(c->stream);
     launch_extract_scatter(c->stream, d_seq, g, nullptr, cur, run.keys, c->l1cap, c->l1cap + 2 * nb + 1);
     c->timer.end(c->stream, "extract_scatter", (double)n);
@@ -805,7 +874,7 @@ static okm_status l1_sampled(okm_ctx *c, const uint8_t *d_seq, uint64_t n, const
                              sizeof(unsigned long long), nb, hipMemcpyDeviceToHost, c->stream));
     OKM_TRY(sync(c));
     if (cap[2 * nb + 1]) {  // some bin outgrew its sampled capacity: redo exactly
-        c->pool->put(run.keys);
+        own.free_all();
         c->hprof.mark("l1.sampled_overflow");
         return OKM_OK;
     }
@@ -820,9 +889,10 @@ static okm_status l1_sampled(okm_ctx *c, const uint8_t *d_seq, uint64_t n, const
     c->l1_ratio = std::max(c->l1_ratio, (double)total / (double)n);
     *placed = true;
     if (total == 0) {
-        c->pool->put(run.keys);
+        own.free_all();
         return OKM_OK;
     }
+    own.disown(run.keys);  // the run owns its keys once it is pushed
     c->runs.push_back(std::move(run));
     c->info.kmers += total;
     c->hprof.mark("l1.sampled");
@@ -830,6 +900,7 @@ static okm_status l1_sampled(okm_ctx *c, const uint8_t *d_seq, uint64_t n, const
 }
 
 static okm_status do_count(okm_ctx *c);
+static void free_run(okm_ctx *c, Run &r);
 
 static okm_status shrink_table(okm_ctx *c, uint64_t **keys, uint64_t **counts, uint64_t n, double slack);
 static okm_status count_general(okm_ctx *c);
@@ -891,7 +962,10 @@ static okm_status result_to_folded_run(okm_ctx *c, Run *out) {
     c->res_host = false;
     c->n_res = 0;
     c->counted = false;
-    if (run.n) OKM_TRY(sorted_run_bins(c, run));
+    if (okm_status st = run.n ? sorted_run_bins(c, run) : OKM_OK; st != OKM_OK) {
+        free_run(c, run);  // (it left the result and reached no run list)
+        return st;
+    }
     *out = std::move(run);
     return OKM_OK;
 }
@@ -909,12 +983,10 @@ static okm_status before_add(okm_ctx *c) {
     c->res_is_input = false;
     Run t;
     OKM_TRY(result_to_folded_run(c, &t));
-    if (t.n) {
+    if (t.n)
         c->runs.push_back(std::move(t));
-    } else {
-        c->pool->put(t.keys);
-        c->pool->put(t.counts);
-    }
+    else
+        free_run(c, t);
     return OKM_OK;
 }
 
@@ -961,12 +1033,10 @@ static okm_status count_unsorted_to_table(okm_ctx *c) {
     release_runs(c, c->runs);
     for (auto &r : keep) c->runs.push_back(std::move(r));
     if (st != OKM_OK) return st;
-    if (t.n) {
+    if (t.n)
         c->runs.push_back(std::move(t));
-    } else if (t.keys) {
-        c->pool->put(t.keys);
-        c->pool->put(t.counts);
-    }
+    else
+        free_run(c, t);
     return OKM_OK;
 }
 
@@ -1106,7 +1176,10 @@ static okm_status fold(okm_ctx *c) {
             if (st == OKM_OK) st = result_to_folded_run(c, &t);
             for (auto &r : host_runs) c->runs.push_back(std::move(r));
             OKM_TRY(st);
-            if (t.n) c->runs.push_back(std::move(t));
+            if (t.n)
+                c->runs.push_back(std::move(t));
+            else
+                free_run(c, t);
         }
     }
     c->hprof.mark("fold");
@@ -1180,13 +1253,15 @@ static okm_status l1_batch(okm_ctx *c, const uint8_t *d_seq, uint64_t n) {
     c->l1_ratio = std::max(c->l1_ratio, (double)total / (double)n);
     c->hprof.mark("l1.hist+sync");
     if (total == 0) return OKM_OK;
-    OKM_TRY(pool_get(*c->pool, run.off.back() * c->kw, &run.keys));
+    Blocks own(*c->pool);
+    OKM_TRY(own.get(run.off.back() * c->kw, &run.keys));
     c->timer.begin(c->stream);
     launch_extract_scatter(c->stream, d_seq, g, c->HC, c->cursor, run.keys, nullptr, nullptr);
     c->timer.end(c->stream, "extract_scatter", (double)n + 8.0 * c->kw * (double)total);
     HIP_TRY(hipGetLastError());
     launch_fill_line_tails(c->stream, c->cursor, c->nbins, run.keys, c->wide);
     HIP_TRY(hipGetLastError());
+    own.disown(run.keys);  // the run owns its keys once it is pushed
     c->runs.push_back(std::move(run));
     c->info.kmers += total;
     c->hprof.mark("l1.scatter_launch");
@@ -1220,7 +1295,7 @@ struct Level {
 static okm_status split_launch_sampled(okm_ctx *c, const std::vector<DevSeg> &psegs,
                                        const std::vector<DevChunk> &chunks, const std::vector<uint32_t> &todo,
                                        const std::vector<uint32_t> &bits, bool weighted, uint32_t max_local,
-                                       std::vector<void *> &level_bufs, Level &L, unsigned long long *ovf);
+                                       Blocks &level, Level &L, unsigned long long *ovf);
 
 // Tile sampling stride of the sampled partition placement.
 static constexpr uint32_t kPartSampleStride = 16;
@@ -1231,7 +1306,7 @@ static constexpr uint32_t kPartSampleStride = 16;
 // slot (the level is then invalid and must be redone exactly).
 static okm_status split_launch(okm_ctx *c, const std::vector<DevSeg> &segtab, const std::vector<Part> &parts,
                                const std::vector<uint32_t> &todo, const std::vector<uint32_t> &bits, bool weighted,
-                               std::vector<void *> &level_bufs, Level &L, unsigned long long *ovf = nullptr) {
+                               Blocks &level, Level &L, unsigned long long *ovf = nullptr) {
     const uint32_t twok = 2u * c->k;
     std::vector<DevSeg> psegs;      // pass segments (one per input segment)
     std::vector<DevChunk> chunks;
@@ -1261,19 +1336,15 @@ static okm_status split_launch(okm_ctx *c, const std::vector<DevSeg> &segtab, co
     L.nout = nout;
     L.total = total;
     OKM_TRY(ensure_hg(c, nout + 1));
-    if (ovf) return split_launch_sampled(c, psegs, chunks, todo, bits, weighted, max_local, level_bufs, L, ovf);
+    if (ovf) return split_launch_sampled(c, psegs, chunks, todo, bits, weighted, max_local, level, L, ovf);
     OKM_TRY(ensure_hc(c, chunks.size() * (size_t)max_local));
     DevSeg *d_segs;
     DevChunk *d_chunks;
     unsigned long long *scan_tmp;
-    OKM_TRY(pool_get(*c->pool, psegs.size(), &d_segs));
-    OKM_TRY(pool_get(*c->pool, chunks.size(), &d_chunks));
-    OKM_TRY(pool_get(*c->pool, (size_t)nout + 1, &L.d_offs));
-    OKM_TRY(pool_get(*c->pool, scan_tmp_elems(nout + 1), &scan_tmp));
-    level_bufs.push_back(d_segs);
-    level_bufs.push_back(d_chunks);
-    level_bufs.push_back(L.d_offs);
-    level_bufs.push_back(scan_tmp);
+    OKM_TRY(level.get(psegs.size(), &d_segs));
+    OKM_TRY(level.get(chunks.size(), &d_chunks));
+    OKM_TRY(level.get((size_t)nout + 1, &L.d_offs));
+    OKM_TRY(level.get(scan_tmp_elems(nout + 1), &scan_tmp));
     OKM_TRY(h2d(c, d_segs, psegs.data(), psegs.size() * sizeof(DevSeg)));
     OKM_TRY(h2d(c, d_chunks, chunks.data(), chunks.size() * sizeof(DevChunk)));
     HIP_TRY(hipMemsetAsync(c->Hg, 0, ((size_t)nout + 1) * sizeof(unsigned long long), c->stream));
@@ -1291,12 +1362,8 @@ static okm_status split_launch(okm_ctx *c, const std::vector<DevSeg> &segtab, co
     OKM_TRY(sync(c));
     c->hprof.mark("split.hist_sync");
     L.padded = padded;  // bins start on 128-B lines (okm_partition.hip)
-    OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(padded, 1) * c->kw, &L.lk));
-    level_bufs.push_back(L.lk);
-    if (weighted) {
-        OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(padded, 1), &L.lc));
-        level_bufs.push_back(L.lc);
-    }
+    OKM_TRY(level.get(std::max<uint64_t>(padded, 1) * c->kw, &L.lk));
+    if (weighted) OKM_TRY(level.get(std::max<uint64_t>(padded, 1), &L.lc));
     c->timer.begin(c->stream);
     launch_part_scatter(c->stream, d_segs, d_chunks, (uint32_t)chunks.size(), max_local, c->HC, c->cursor, L.lk, L.lc,
                         c->wide);
@@ -1309,7 +1376,7 @@ static okm_status split_launch(okm_ctx *c, const std::vector<DevSeg> &segtab, co
 static okm_status split_launch_sampled(okm_ctx *c, const std::vector<DevSeg> &psegs,
                                        const std::vector<DevChunk> &chunks, const std::vector<uint32_t> &todo,
                                        const std::vector<uint32_t> &bits, bool weighted, uint32_t max_local,
-                                       std::vector<void *> &level_bufs, Level &L, unsigned long long *ovf) {
+                                       Blocks &level, Level &L, unsigned long long *ovf) {
     const uint32_t S = kPartSampleStride, nout = L.nout;
     L.d_ovf = ovf;
     const uint64_t piece = kChunkKeys / S;
@@ -1345,22 +1412,17 @@ static okm_status split_launch_sampled(okm_ctx *c, const std::vector<DevSeg> &ps
                  o_cp = pack.add(cp);
     uint8_t *blob;
     unsigned long long *scan_tmp;
-    OKM_TRY(pool_get(*c->pool, pack.bytes.size(), &blob));
-    OKM_TRY(pool_get(*c->pool, (size_t)nout + 1, &L.d_offs));
-    OKM_TRY(pool_get(*c->pool, (size_t)nout, &L.d_ends));
-    OKM_TRY(pool_get(*c->pool, scan_tmp_elems(nout + 1), &scan_tmp));
-    for (void *p : {(void *)blob, (void *)L.d_offs, (void *)L.d_ends, (void *)scan_tmp}) level_bufs.push_back(p);
+    OKM_TRY(level.get(pack.bytes.size(), &blob));
+    OKM_TRY(level.get((size_t)nout + 1, &L.d_offs));
+    OKM_TRY(level.get((size_t)nout, &L.d_ends));
+    OKM_TRY(level.get(scan_tmp_elems(nout + 1), &scan_tmp));
     DevSeg *d_segs = reinterpret_cast<DevSeg *>(blob + o_segs);
     DevChunk *d_chunks = reinterpret_cast<DevChunk *>(blob + o_chunks);
     DevChunk *d_sample = reinterpret_cast<DevChunk *>(blob + o_sample);
     DevCapParent *d_cp = reinterpret_cast<DevCapParent *>(blob + o_cp);
     L.padded = (uint64_t)limit;
-    OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(L.padded, 1) * c->kw, &L.lk));
-    level_bufs.push_back(L.lk);
-    if (weighted) {
-        OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(L.padded, 1), &L.lc));
-        level_bufs.push_back(L.lc);
-    }
+    OKM_TRY(level.get(std::max<uint64_t>(L.padded, 1) * c->kw, &L.lk));
+    if (weighted) OKM_TRY(level.get(std::max<uint64_t>(L.padded, 1), &L.lc));
     OKM_TRY(h2d(c, blob, pack.bytes.data(), pack.bytes.size()));
     HIP_TRY(hipMemsetAsync(c->Hg, 0, ((size_t)nout + 1) * sizeof(unsigned long long), c->stream));
     uint64_t sampled_keys = 0;
@@ -1462,7 +1524,8 @@ static okm_status shrink_table(okm_ctx *c, uint64_t **keys, uint64_t **counts, u
     // 3.4 G keys of folded tables in 127 GB of blocks instead of 54 GB)
     const uint64_t kpad = (kb + 255) & ~255ull;
     uint8_t *blk;
-    OKM_TRY(pool_get(*c->pool, kpad + cb, &blk));
+    Blocks own(*c->pool);
+    OKM_TRY(own.get(kpad + cb, &blk));
     uint64_t *nk = reinterpret_cast<uint64_t *>(blk), *nc = reinterpret_cast<uint64_t *>(blk + kpad);
     if (n) {
         HIP_TRY(hipMemcpyAsync(nk, *keys, kb, hipMemcpyDeviceToDevice, c->stream));
@@ -1471,6 +1534,7 @@ static okm_status shrink_table(okm_ctx *c, uint64_t **keys, uint64_t **counts, u
     OKM_TRY(sync(c));
     c->pool->put(*keys);
     c->pool->put(*counts);
+    own.disown(blk);  // the table's owner has the new block from here
     *keys = nk;
     *counts = nc;
     return OKM_OK;
@@ -1496,17 +1560,18 @@ struct ResDst {
 // an instance-bound table would hold 16 B per instance instead of per
 // distinct key, 3.6x more at C2).  Into a caller's table (dst: key-range
 // groups) the compaction is launched with the count, before the sync.
-// Releases level_bufs, d_items and d_segs.
+// Takes `level` (the level arrays and what dies with them) and `items`
+// (d_items and d_segs) over: both are empty when it returns OK.
 // last_use: no run is read after this count (its items lie in level arrays,
 // and c->may_take_runs: the runs are released once counted); the staged keys
 // then go into the smallest run block that holds them, when one does.
 // guard (a speculative launch over round-0 items, make_items' flags): the
 // kernels return at once when guard[0] or guard[1] is set; then *aborted is
-// set, hguard[0..2] receives the flags, and the caller keeps level_bufs,
-// d_items and d_segs.
+// set, hguard[0..2] receives the flags, and the caller still has `level` and
+// `items`.
 static okm_status count_and_compact(okm_ctx *c, DevItem *d_items, DevSeg *d_segs, uint32_t nitems,
-                                    uint64_t out_total, uint64_t in_total, bool weighted,
-                                    std::vector<void *> &level_bufs, const unsigned long long *guard = nullptr,
+                                    uint64_t out_total, uint64_t in_total, bool weighted, Blocks &level,
+                                    Blocks &items, const unsigned long long *guard = nullptr,
                                     unsigned long long *hguard = nullptr, bool *aborted = nullptr,
                                     const unsigned long long *d_nitems = nullptr, const ResDst *dst = nullptr,
                                     bool last_use = false, bool in_place = false) {
@@ -1530,41 +1595,30 @@ static okm_status count_and_compact(okm_ctx *c, DevItem *d_items, DevSeg *d_segs
             if (b >= need && (!best || b < best)) best = b, sk = r.keys;
         }
     }
-    const bool donated = sk != nullptr;
-    // a failure once the count may have written into a run: the input is gone
-    struct Lost {
-        okm_ctx *c;
-        bool on;
-        ~Lost() {
-            if (on) c->input_lost = true;
-        }
-    } lost{c, false};
-    if (!donated && !in_place && !direct) OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(out_total, 1) * c->kw, &sk));
-    if (!direct) OKM_TRY(pool_get(*c->pool, sc_words, &sc));
-    OKM_TRY(pool_get(*c->pool, nitems + 1, &n_out));
-    OKM_TRY(pool_get(*c->pool, nitems + 1, &dense_off));
-    OKM_TRY(pool_get(*c->pool, scan_tmp_elems(nitems + 1), &scan_tmp));
+    const bool donated = sk != nullptr;  // a run's block: it stays the run's (never in `own`)
+    Lost lost{c};
+    Blocks own(*c->pool);  // this count's staging and scratch
+    if (!donated && !in_place && !direct) OKM_TRY(own.get(std::max<uint64_t>(out_total, 1) * c->kw, &sk));
+    if (!direct) OKM_TRY(own.get(sc_words, &sc));
+    OKM_TRY(own.get(nitems + 1, &n_out));
+    OKM_TRY(own.get(nitems + 1, &dense_off));
+    OKM_TRY(own.get(scan_tmp_elems(nitems + 1), &scan_tmp));
     uint32_t *defer = nullptr;             // deferred items (tag kernel)
     unsigned long long *status = nullptr;  // per-item look-back words (direct)
     if (direct)
-        OKM_TRY(pool_get(*c->pool, nitems, &status));
+        OKM_TRY(own.get(nitems, &status));
     else
-        OKM_TRY(pool_get(*c->pool, nitems, &defer));
-    auto release_own = [&]() {
-        for (void *p : {(void *)sk, (void *)sc, (void *)n_out, (void *)dense_off, (void *)scan_tmp, (void *)defer,
-                        (void *)status})
-            if (p && !(donated && p == (void *)sk)) c->pool->put(p);
-    };
+        OKM_TRY(own.get(nitems, &defer));
+    // the level arrays die with the segments that point into them; the items outlive both
     auto release_level = [&]() {
-        for (void *p : level_bufs) c->pool->put(p);
-        level_bufs.clear();
-        c->pool->put(d_segs);
+        level.free_all();
+        items.put(d_segs);
     };
     if (c->hprof.on) {
         uint64_t rb = 0;
         for (auto &r : c->runs) rb += run_device_bytes(c, r);
         size_t lb = 0;
-        for (void *p : level_bufs) lb += c->pool->size_of(p);
+        for (void *p : level.held()) lb += c->pool->size_of(p);
         fprintf(stderr, "[okm count] %u items, %.3f G keys: in use %.1f GB (runs %.1f, level %.1f, staged counts %.1f, "
                         "staged keys %.1f GB)\n", nitems, in_total / 1e9, c->pool->in_use() / 1e9, rb / 1e9, lb / 1e9,
                 c->pool->size_of(sc) / 1e9, (sk && !donated ? c->pool->size_of(sk) : 0) / 1e9);
@@ -1611,9 +1665,9 @@ static okm_status count_and_compact(okm_ctx *c, DevItem *d_items, DevSeg *d_segs
         HIP_TRY(hipMemcpyAsync(&hs[1], c->flag, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         if (guard) HIP_TRY(hipMemcpyAsync(&hs[2], guard, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         lost.on = false;  // (groups never write into a run)
-        release_own();
-        release_level();
-        c->pool->put(d_items);
+        own.free_all();
+        level.free_all();
+        items.free_all();
         if (aborted) *aborted = false;  // (known at the sync: count_grouped recounts every group then)
         c->n_res = 0;
         return OKM_OK;
@@ -1637,7 +1691,7 @@ static okm_status count_and_compact(okm_ctx *c, DevItem *d_items, DevSeg *d_segs
         *aborted = (hv[2] | hv[3]) != 0;
         if (*aborted) {  // the kernels returned at once: nothing was written
             lost.on = false;
-            release_own();
+            own.free_all();
             return OKM_OK;
         }
     }
@@ -1645,10 +1699,10 @@ static okm_status count_and_compact(okm_ctx *c, DevItem *d_items, DevSeg *d_segs
         // a count past 2^32 in the u32 staging: count again with u64 counts
         // (the input is intact: staging was separate, nothing was compacted)
         c->hprof.mark("count.narrow_overflow");
-        c->pool->put(sc);
+        own.put(sc);
         sc = nullptr;
         narrow = false;
-        OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(out_total, 1), &sc));
+        OKM_TRY(own.get(std::max<uint64_t>(out_total, 1), &sc));
         HIP_TRY(hipMemsetAsync(c->flag, 0, 2 * sizeof(unsigned long long), c->stream));
         HIP_TRY(hipMemsetAsync(d_nitems ? n_out : n_out + nitems, 0,
                                (d_nitems ? nitems + 1 : 1) * sizeof(unsigned long long), c->stream));
@@ -1660,12 +1714,7 @@ static okm_status count_and_compact(okm_ctx *c, DevItem *d_items, DevSeg *d_segs
         HIP_TRY(hipMemcpyAsync(&hv[1], c->flag, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         OKM_TRY(sync(c));
     }
-    if (hv[1]) {  // give every buffer of the step back before failing (long-lived contexts)
-        release_own();
-        release_level();
-        c->pool->put(d_items);
-        return fail(OKM_E_DEVICE, "count_items invariant violated (code " + std::to_string(hv[1]) + ")");
-    }
+    if (hv[1]) return fail(OKM_E_DEVICE, "count_items invariant violated (code " + std::to_string(hv[1]) + ")");
     const uint64_t nd = hv[0];
     const uint32_t nkept = d_nitems ? (uint32_t)std::min<unsigned long long>(nitems, hv[5]) : nitems;
     const double staged = 8.0 * c->kw + (narrow ? 4.0 : 8.0);  // per distinct key: staged (key, count)
@@ -1680,7 +1729,6 @@ static okm_status count_and_compact(okm_ctx *c, DevItem *d_items, DevSeg *d_segs
     // block may (the runs' last use: their keys went into the level arrays)
     const size_t kpad = (std::max<uint64_t>(nd, 1) * 8 * c->kw + 255) & ~(size_t)255;
     const size_t need = kpad + std::max<uint64_t>(nd, 1) * 8;
-    uint8_t *blk = nullptr;
     if (!dst && in_place && last_use && c->may_take_runs) {
         // the runs are dead (their keys were partitioned into the level
         // arrays, where the compaction reads the staged runs): their blocks go
@@ -1693,16 +1741,6 @@ static okm_status count_and_compact(okm_ctx *c, DevItem *d_items, DevSeg *d_segs
             r.keys = r.counts = nullptr;
         }
         c->took_runs = true;  // (the runs are released after the count)
-    } else if (!dst && !in_place && c->share_result) {  // the smallest level block that holds keys and counts
-        size_t best = 0, at = 0;
-        for (size_t i = 0; i < level_bufs.size(); ++i) {
-            const size_t b = c->pool->size_of(level_bufs[i]);
-            if (b >= need && (!best || b < best)) best = b, at = i;
-        }
-        if (best) {
-            blk = static_cast<uint8_t *>(level_bufs[at]);
-            level_bufs.erase(level_bufs.begin() + at);
-        }
     }
     if (!dst && !donated && c->share_result) {
         // the table stays as the items' sorted runs (okm_ctx::Pending): the
@@ -1720,14 +1758,12 @@ static okm_status count_and_compact(okm_ctx *c, DevItem *d_items, DevSeg *d_segs
         p.sk = in_place ? nullptr : sk;
         p.sc = sc;
         p.narrow = narrow;
-        p.hold = level_bufs;
-        for (void *q : {(void *)d_segs, (void *)d_items, (void *)n_out, (void *)dense_off, (void *)sc, (void *)p.sk})
-            if (q && !(q == (void *)d_segs && !in_place)) p.hold.push_back(q);
-        level_bufs.clear();
-        sc = nullptr;
-        sk = nullptr;
-        n_out = dense_off = nullptr;
-        release_own();
+        own.put(scan_tmp);
+        own.put(defer);
+        // the rest is the pending table's: freed with it (drop_pending)
+        level.move_to(p.hold);
+        items.move_to(p.hold);
+        own.move_to(p.hold);
         c->n_res = nd;
         c->info.distinct = nd;
         c->counted = true;
@@ -1735,14 +1771,22 @@ static okm_status count_and_compact(okm_ctx *c, DevItem *d_items, DevSeg *d_segs
         c->hprof.dump("count");
         return OKM_OK;
     }
+    uint8_t *blk = nullptr;
+    if (!dst && !in_place && c->share_result) {  // the smallest level block that holds keys and counts
+        size_t best = 0;
+        for (void *p : level.held()) {
+            const size_t b = c->pool->size_of(p);
+            if (b >= need && (!best || b < best)) best = b, blk = static_cast<uint8_t *>(p);
+        }
+        level.disown(blk);  // the level block becomes the result: published below
+    }
     if (!in_place) release_level();
     if (!dst) {
         if (blk) {
             c->res_keys = reinterpret_cast<uint64_t *>(blk);
-            c->res_counts = reinterpret_cast<uint64_t *>(blk + kpad);  // inside the block: the pool ignores it on put
+            c->res_counts = reinterpret_cast<uint64_t *>(blk + kpad);  // inside the block: never owned on its own
         } else {
-            OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(nd, 1) * c->kw, &c->res_keys));
-            OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(nd, 1), &c->res_counts));
+            OKM_TRY(get_result(c, nd));
         }
         c->timer.begin(c->stream);
         launch_compact_items(c->stream, d_items, nkept, n_out, dense_off, sk, sc, c->res_keys, c->res_counts, c->wide,
@@ -1751,9 +1795,9 @@ static okm_status count_and_compact(okm_ctx *c, DevItem *d_items, DevSeg *d_segs
         HIP_TRY(hipGetLastError());
     }
     OKM_TRY(sync(c));  // the result is complete (and a group's buffers may serve the next group)
-    if (in_place) release_level();
-    c->pool->put(d_items);
-    release_own();
+    level.free_all();  // (in place: the level arrays held the staged runs until now)
+    items.free_all();
+    own.free_all();
     lost.on = false;
     c->took_runs |= donated;
     c->n_res = nd;
@@ -1779,8 +1823,9 @@ static okm_status partition_pairs(okm_ctx *c, const uint64_t *d_keys, const uint
     for (uint64_t o = 0; o < n; o += kChunkKeys) chunks.push_back(DevChunk{0, 0, o, std::min(kChunkKeys, n - o)});
     DevSeg *d_seg;
     DevChunk *d_chunks;
-    OKM_TRY(pool_get(*c->pool, 1, &d_seg));
-    OKM_TRY(pool_get(*c->pool, chunks.size(), &d_chunks));
+    Blocks own(*c->pool);
+    OKM_TRY(own.get(1, &d_seg));
+    OKM_TRY(own.get(chunks.size(), &d_chunks));
     HIP_TRY(hipMemcpyAsync(d_seg, &s, sizeof(DevSeg), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * sizeof(DevChunk), hipMemcpyHostToDevice, c->stream));
     OKM_TRY(ensure_hc(c, chunks.size() * (size_t)c->nbins));
@@ -1791,16 +1836,17 @@ static okm_status partition_pairs(okm_ctx *c, const uint64_t *d_keys, const uint
     c->timer.end(c->stream, "part_hist", 8.0 * c->kw * (double)n);
     HIP_TRY(hipGetLastError());
     OKM_TRY(hist_to_offsets(c, c->nbins, run.off));
-    OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(run.off.back(), 1) * c->kw, &run.keys));
-    OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(run.off.back(), 1), &run.counts));
+    OKM_TRY(own.get(std::max<uint64_t>(run.off.back(), 1) * c->kw, &run.keys));
+    OKM_TRY(own.get(std::max<uint64_t>(run.off.back(), 1), &run.counts));
     c->timer.begin(c->stream);
     launch_part_scatter(c->stream, d_seg, d_chunks, (uint32_t)chunks.size(), c->nbins, c->HC, c->cursor, run.keys,
                         run.counts, c->wide);
     c->timer.end(c->stream, "part_scatter", (16.0 + 16.0 * c->kw) * (double)n);
     HIP_TRY(hipGetLastError());
     OKM_TRY(sync(c));
-    c->pool->put(d_seg);
-    c->pool->put(d_chunks);
+    own.disown(run.keys);  // the caller's run owns both from here
+    own.disown(run.counts);
+    own.free_all();
     return OKM_OK;
 }
 
@@ -1808,19 +1854,13 @@ static okm_status partition_pairs(okm_ctx *c, const uint64_t *d_keys, const uint
 // The k-way merge of sorted runs (okm_merge.hip) in two passes: distinct
 // keys per item, exclusive scan, then the merge writes every item's keys and
 // summed counts straight into the exact-size result table (no staging, no
-// compaction).  Releases bufs, d_items and d_segs.
+// compaction).  Takes bufs (the plan's tables, d_items and d_segs) over.
 static okm_status merge_sorted_items(okm_ctx *c, DevItem *d_items, DevSeg *d_segs, uint32_t nitems, uint64_t in_total,
-                                     bool weighted, std::vector<void *> &bufs) {
+                                     bool weighted, Blocks &bufs) {
     unsigned long long *n_out, *dense_off, *scan_tmp;
-    OKM_TRY(pool_get(*c->pool, (size_t)nitems + 1, &n_out));
-    OKM_TRY(pool_get(*c->pool, (size_t)nitems + 1, &dense_off));
-    OKM_TRY(pool_get(*c->pool, scan_tmp_elems(nitems + 1), &scan_tmp));
-    for (void *p : {(void *)n_out, (void *)dense_off, (void *)scan_tmp, (void *)d_items, (void *)d_segs})
-        bufs.push_back(p);
-    auto release = [&]() {
-        for (void *p : bufs) c->pool->put(p);
-        bufs.clear();
-    };
+    OKM_TRY(bufs.get((size_t)nitems + 1, &n_out));
+    OKM_TRY(bufs.get((size_t)nitems + 1, &dense_off));
+    OKM_TRY(bufs.get(scan_tmp_elems(nitems + 1), &scan_tmp));
     HIP_TRY(hipMemsetAsync(c->flag, 0, 2 * sizeof(unsigned long long), c->stream));
     HIP_TRY(hipMemsetAsync(n_out + nitems, 0, sizeof(unsigned long long), c->stream));
     c->timer.begin(c->stream);
@@ -1834,13 +1874,9 @@ static okm_status merge_sorted_items(okm_ctx *c, DevItem *d_items, DevSeg *d_seg
     HIP_TRY(hipMemcpyAsync(&hv[0], dense_off + nitems, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(&hv[1], c->flag, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     OKM_TRY(sync(c));
-    if (hv[1]) {
-        release();
-        return fail(OKM_E_DEVICE, "merge_items invariant violated (code " + std::to_string(hv[1]) + ")");
-    }
+    if (hv[1]) return fail(OKM_E_DEVICE, "merge_items invariant violated (code " + std::to_string(hv[1]) + ")");
     const uint64_t nd = hv[0];
-    OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(nd, 1) * c->kw, &c->res_keys));
-    OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(nd, 1), &c->res_counts));
+    OKM_TRY(get_result(c, nd));
     c->timer.begin(c->stream);
     launch_merge_items(c->stream, d_items, nitems, d_segs, n_out, dense_off, c->res_keys, c->res_counts, c->flag,
                        weighted, c->wide, true);
@@ -1848,7 +1884,7 @@ static okm_status merge_sorted_items(okm_ctx *c, DevItem *d_items, DevSeg *d_seg
                  (8.0 * c->kw + (weighted ? 8.0 : 0.0)) * (double)in_total + (8.0 * c->kw + 8.0) * (double)nd);
     HIP_TRY(hipGetLastError());
     OKM_TRY(sync(c));  // borrowed runs (okm_add_sorted_pairs_device) may be freed once okm_count returns
-    release();
+    bufs.free_all();
     c->n_res = nd;
     c->info.distinct = nd;
     c->counted = true;
@@ -1861,26 +1897,16 @@ static okm_status merge_sorted_items(okm_ctx *c, DevItem *d_items, DevSeg *d_seg
 // keys (nothing written), an exclusive scan, then the same items counted
 // again straight into the exact-size result table at their scanned offsets.
 // Same memory as the k-way merge kernel (no instance-bound staging, no
-// compaction) at the count kernels' speed.  Releases bufs, d_items, d_segs.
+// compaction) at the count kernels' speed.  Takes bufs (the plan's tables,
+// d_items and d_segs) over.
 static okm_status count_sorted_two_pass(okm_ctx *c, DevItem *d_items, DevSeg *d_segs, uint32_t nitems,
-                                        uint64_t in_total, std::vector<void *> &bufs) {
-    bufs.push_back(d_items);
-    bufs.push_back(d_segs);
-    auto release = [&]() {
-        for (void *p : bufs) c->pool->put(p);
-        bufs.clear();
-    };
+                                        uint64_t in_total, Blocks &bufs) {
     unsigned long long *n_out = nullptr, *dense_off = nullptr, *scan_tmp = nullptr;
     uint32_t *defer = nullptr;
-    okm_status st = pool_get(*c->pool, (size_t)nitems + 1, &n_out);
-    if (st == OKM_OK) bufs.push_back(n_out), st = pool_get(*c->pool, (size_t)nitems + 1, &dense_off);
-    if (st == OKM_OK) bufs.push_back(dense_off), st = pool_get(*c->pool, scan_tmp_elems(nitems + 1), &scan_tmp);
-    if (st == OKM_OK) bufs.push_back(scan_tmp), st = pool_get(*c->pool, (size_t)nitems, &defer);
-    if (st != OKM_OK) {
-        release();
-        return st;
-    }
-    bufs.push_back(defer);
+    OKM_TRY(bufs.get((size_t)nitems + 1, &n_out));
+    OKM_TRY(bufs.get((size_t)nitems + 1, &dense_off));
+    OKM_TRY(bufs.get(scan_tmp_elems(nitems + 1), &scan_tmp));
+    OKM_TRY(bufs.get((size_t)nitems, &defer));
     const double in_bytes = (8.0 * c->kw + 8.0) * (double)in_total;
     HIP_TRY(hipMemsetAsync(c->flag, 0, 2 * sizeof(unsigned long long), c->stream));
     HIP_TRY(hipMemsetAsync(n_out + nitems, 0, sizeof(unsigned long long), c->stream));
@@ -1895,18 +1921,9 @@ static okm_status count_sorted_two_pass(okm_ctx *c, DevItem *d_items, DevSeg *d_
     HIP_TRY(hipMemcpyAsync(&hv[0], dense_off + nitems, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(&hv[1], c->flag, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     OKM_TRY(sync(c));
-    if (hv[1]) {
-        release();
-        return fail(OKM_E_DEVICE, "count_items invariant violated (code " + std::to_string(hv[1]) + ")");
-    }
+    if (hv[1]) return fail(OKM_E_DEVICE, "count_items invariant violated (code " + std::to_string(hv[1]) + ")");
     const uint64_t nd = hv[0];
-    st = pool_get(*c->pool, std::max<uint64_t>(nd, 1) * c->kw, &c->res_keys);
-    if (st == OKM_OK) st = pool_get(*c->pool, std::max<uint64_t>(nd, 1), &c->res_counts);
-    if (st != OKM_OK) {
-        release();
-        invalidate_result(c);
-        return st;
-    }
+    OKM_TRY(get_result(c, nd));
     launch_set_out_off(c->stream, d_items, nitems, dense_off);
     HIP_TRY(hipMemsetAsync(c->flag, 0, 2 * sizeof(unsigned long long), c->stream));
     c->timer.begin(c->stream);
@@ -1916,7 +1933,7 @@ static okm_status count_sorted_two_pass(okm_ctx *c, DevItem *d_items, DevSeg *d_
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&hv[1], c->flag, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     OKM_TRY(sync(c));  // borrowed runs (okm_add_sorted_pairs_device) may be freed once okm_count returns
-    release();
+    bufs.free_all();
     if (hv[1]) return fail(OKM_E_DEVICE, "count_items invariant violated (code " + std::to_string(hv[1]) + ")");
     c->n_res = nd;
     c->info.distinct = nd;
@@ -2039,25 +2056,22 @@ static okm_status count_sorted_plan(okm_ctx *c, bool *fallback, std::vector<uint
         c->info.distinct = 0;
         return OKM_OK;
     }
-    std::vector<void *> bufs;
+    Blocks bufs(*c->pool), items(*c->pool);  // the plan's tables; d_items and d_segs
     DevSortedPart *d_parts;
     DevSeg *d_rbins, *d_segs;
     DevItem *d_items;
     unsigned long long *itemtot, *offs, *tmp, *flags;
-    OKM_TRY(pool_get(*c->pool, parts.size(), &d_parts));
-    OKM_TRY(pool_get(*c->pool, rbins.size(), &d_rbins));
-    OKM_TRY(pool_get(*c->pool, (size_t)nitems * R, &d_segs));
-    OKM_TRY(pool_get(*c->pool, nitems, &d_items));
-    OKM_TRY(pool_get(*c->pool, (size_t)nitems + 1, &itemtot));
-    OKM_TRY(pool_get(*c->pool, (size_t)nitems + 1, &offs));
-    OKM_TRY(pool_get(*c->pool, scan_tmp_elems(nitems + 1), &tmp));
-    OKM_TRY(pool_get(*c->pool, 2, &flags));
+    OKM_TRY(bufs.get(parts.size(), &d_parts));
+    OKM_TRY(bufs.get(rbins.size(), &d_rbins));
+    OKM_TRY(items.get((size_t)nitems * R, &d_segs));
+    OKM_TRY(items.get(nitems, &d_items));
+    OKM_TRY(bufs.get((size_t)nitems + 1, &itemtot));
+    OKM_TRY(bufs.get((size_t)nitems + 1, &offs));
+    OKM_TRY(bufs.get(scan_tmp_elems(nitems + 1), &tmp));
+    OKM_TRY(bufs.get(2, &flags));
     unsigned long long *bounds, *part_max;
-    OKM_TRY(pool_get(*c->pool, std::max<size_t>((size_t)nitems * R, 1), &bounds));
-    OKM_TRY(pool_get(*c->pool, parts.size(), &part_max));
-    for (void *p : {(void *)d_parts, (void *)d_rbins, (void *)itemtot, (void *)offs, (void *)tmp, (void *)flags,
-                    (void *)bounds, (void *)part_max})
-        bufs.push_back(p);
+    OKM_TRY(bufs.get(std::max<size_t>((size_t)nitems * R, 1), &bounds));
+    OKM_TRY(bufs.get(parts.size(), &part_max));
     OKM_TRY(h2d(c, d_parts, parts.data(), parts.size() * sizeof(DevSortedPart)));
     OKM_TRY(h2d(c, d_rbins, rbins.data(), rbins.size() * sizeof(DevSeg)));
     HIP_TRY(hipMemsetAsync(flags, 0, 2 * sizeof(unsigned long long), c->stream));
@@ -2105,9 +2119,8 @@ static okm_status count_sorted_plan(okm_ctx *c, bool *fallback, std::vector<uint
                         (unsigned long long)r.n, r.sorted, r.folded, r.borrowed,
                         (unsigned long long)(r.off.empty() ? 0 : r.off.back()));
         }
-        for (void *p : bufs) c->pool->put(p);
-        c->pool->put(d_segs);
-        c->pool->put(d_items);
+        bufs.free_all();
+        items.free_all();
         *fallback = true;
         return OKM_OK;
     }
@@ -2131,11 +2144,13 @@ static okm_status count_sorted_plan(okm_ctx *c, bool *fallback, std::vector<uint
     const bool tight = need > 0.9 * device_room(c);
     // weighted runs at the limit: the count kernels in two passes
     // (tools/merge8_cost.py, 8 runs: see DESIGN.md §8)
-    if (weighted && (mkv == 2 || (tight && mkv != 1)))
-        return count_sorted_two_pass(c, d_items, d_segs, nitems, in_total, bufs);
+    const bool two_pass = weighted && (mkv == 2 || (tight && mkv != 1));
     const bool merge = (mkv == 1 || tight) && R <= merge_max_runs() && item_max <= merge_item_capacity();
-    if (merge) return merge_sorted_items(c, d_items, d_segs, nitems, in_total, weighted, bufs);
-    return count_and_compact(c, d_items, d_segs, nitems, in_total, in_total, weighted, bufs);
+    if (!two_pass && !merge)
+        return count_and_compact(c, d_items, d_segs, nitems, in_total, in_total, weighted, bufs, items);
+    items.move_to(bufs);  // (these two free everything at one point)
+    if (two_pass) return count_sorted_two_pass(c, d_items, d_segs, nitems, in_total, bufs);
+    return merge_sorted_items(c, d_items, d_segs, nitems, in_total, weighted, bufs);
 }
 
 struct CountPlan {
@@ -2243,8 +2258,7 @@ static okm_status do_count_runs(okm_ctx *c) {
         // holds): it already is the result — copied, since it may be borrowed
         Run &r = c->runs[0];
         const uint64_t n = r.n;
-        OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(n, 1) * c->kw, &c->res_keys));
-        OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(n, 1), &c->res_counts));
+        OKM_TRY(get_result(c, n));
         c->timer.begin(c->stream);
         if (n) {
             HIP_TRY(hipMemcpyAsync(c->res_keys, r.keys, n * c->kw * sizeof(uint64_t), hipMemcpyDeviceToDevice,
@@ -2313,9 +2327,10 @@ static okm_status count_spilled(okm_ctx *c) {
         for (auto &r : all)
             if (r.host) host_pairs += r.off[b1] - r.off[b0];
         uint64_t *uk = nullptr, *uc = nullptr;
+        Blocks upload(*c->pool);  // the group's slices of the host runs
         if (host_pairs) {
-            st = pool_get(*c->pool, host_pairs * kw, &uk);
-            if (st == OKM_OK && weighted) st = pool_get(*c->pool, host_pairs, &uc);
+            st = upload.get(host_pairs * kw, &uk);
+            if (st == OKM_OK && weighted) st = upload.get(host_pairs, &uc);
         }
         std::vector<Run> grp;
         uint64_t at = 0;
@@ -2375,8 +2390,7 @@ static okm_status count_spilled(okm_ctx *c) {
             }
             invalidate_result(c);
         }
-        c->pool->put(uk);
-        c->pool->put(uc);
+        upload.free_all();
         ++groups;
         b0 = b1;
     }
@@ -2386,8 +2400,7 @@ static okm_status count_spilled(okm_ctx *c) {
     // the result: on the device when it fits beside what is left, else on the host
     const uint64_t nd = hc.size();
     if ((double)nd * (8.0 * kw + 8.0) <= 0.8 * device_room(c)) {
-        OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(nd, 1) * kw, &c->res_keys));
-        OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(nd, 1), &c->res_counts));
+        OKM_TRY(get_result(c, nd));
         if (nd) {
             HIP_TRY(hipMemcpyAsync(c->res_keys, hk.data(), nd * 8 * kw, hipMemcpyHostToDevice, c->stream));
             HIP_TRY(hipMemcpyAsync(c->res_counts, hc.data(), nd * 8, hipMemcpyHostToDevice, c->stream));
@@ -2486,7 +2499,9 @@ static okm_status count_parts(okm_ctx *c, std::vector<DevSeg> &segtab, std::vect
         return std::min(b, rem);
     };
 
-    std::vector<void *> level_bufs;
+    // every level array of every round (and what dies with them); the items
+    // and segments of the count in progress
+    Blocks level(*c->pool), items(*c->pool);
     DevItem *d_items = nullptr;
     DevSeg *d_segs = nullptr;
     uint32_t nitems = 0;
@@ -2539,48 +2554,35 @@ static okm_status count_parts(okm_ctx *c, std::vector<DevSeg> &segtab, std::vect
             for (int attempt = 0;; ++attempt) {
                 unsigned long long *flags;  // [0] children too big, [1] 1: slot overflow | 2: 64-bit counts, [2] max,
                                             // [3] / [4] fan-out jobs (small / large)
-                OKM_TRY(pool_get(*c->pool, 5, &flags));
-                level_bufs.push_back(flags);
+                OKM_TRY(level.get(5, &flags));
                 HIP_TRY(hipMemsetAsync(flags, 0, 5 * sizeof(unsigned long long), c->stream));
                 Level L;
-                OKM_TRY(split_launch(c, segtab, parts, all, bits, weighted, level_bufs, L,
+                OKM_TRY(split_launch(c, segtab, parts, all, bits, weighted, level, L,
                                      try_sampled && !attempt ? flags + 1 : nullptr));
                 std::vector<DevParent> par(parts.size());
                 for (uint32_t i = 0; i < parts.size(); ++i)
                     par[i] = DevParent{L.out_base[i], twok - parts[i].consumed - bits[i]};
                 DevParent *d_par;
-                OKM_TRY(pool_get(*c->pool, par.size(), &d_par));
+                OKM_TRY(level.get(par.size(), &d_par));
                 const uint32_t nslots = L.nout << fan.bits;
                 const unsigned long long *d_nitems = nullptr;  // fan-out: items kept, on the device
-                OKM_TRY(pool_get(*c->pool, nslots, &d_items));
-                OKM_TRY(pool_get(*c->pool, nslots, &d_segs));
-                level_bufs.push_back(d_par);
-                if (fan.bits) {
-                    OKM_TRY(pool_get(*c->pool, L.nout, &fan.jobs));
-                    level_bufs.push_back(fan.jobs);
-                }
+                OKM_TRY(items.get(nslots, &d_items));
+                OKM_TRY(items.get(nslots, &d_segs));
+                if (fan.bits) OKM_TRY(level.get(L.nout, &fan.jobs));
                 OKM_TRY(h2d(c, d_par, par.data(), par.size() * sizeof(DevParent)));
                 // items stage their runs densely: slots = the pass's keys, not the
                 // level's sampled capacity (~1.5x the keys at C2)
                 unsigned long long *doff, *dtmp;
-                OKM_TRY(pool_get(*c->pool, (size_t)L.nout + 1, &doff));
-                OKM_TRY(pool_get(*c->pool, scan_tmp_elems(L.nout + 1), &dtmp));
-                level_bufs.push_back(doff);
-                level_bufs.push_back(dtmp);
+                OKM_TRY(level.get((size_t)L.nout + 1, &doff));
+                OKM_TRY(level.get(scan_tmp_elems(L.nout + 1), &dtmp));
                 launch_child_offsets(c->stream, L.d_offs, L.d_ends, L.nout, doff, dtmp);
                 launch_make_items(c->stream, L.d_offs, L.d_ends, L.nout, d_par, (uint32_t)par.size(), L.lk, L.lc,
                                   d_items, d_segs, item_max, capbits, flags, c->kw, fan, doff);
                 HIP_TRY(hipGetLastError());
                 if (fan.bits) {  // oversized children split into a second level array (same offsets), or in place
                     uint64_t *fk = L.lk, *fc = nullptr;
-                    if (!fan_in_place) {
-                        OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(L.padded, 1) * c->kw, &fk));
-                        level_bufs.push_back(fk);
-                    }
-                    if (L.lc) {
-                        OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(L.padded, 1), &fc));
-                        level_bufs.push_back(fc);
-                    }
+                    if (!fan_in_place) OKM_TRY(level.get(std::max<uint64_t>(L.padded, 1) * c->kw, &fk));
+                    if (L.lc) OKM_TRY(level.get(std::max<uint64_t>(L.padded, 1), &fc));
                     c->timer.begin(c->stream);
                     launch_fan_split(c->stream, fan.jobs, L.nout, flags, L.lk, L.lc, fk, fc, d_items, d_segs, item_max,
                                      capbits, flags, c->wide);
@@ -2589,13 +2591,14 @@ static okm_status count_parts(okm_ctx *c, std::vector<DevSeg> &segtab, std::vect
                     // drop the empty slots, so the count kernels deal real items only
                     DevItem *dense_items;
                     unsigned long long *iflags, *ipos, *itmp;
-                    OKM_TRY(pool_get(*c->pool, nslots, &dense_items));
-                    OKM_TRY(pool_get(*c->pool, (size_t)nslots + 1, &iflags));
-                    OKM_TRY(pool_get(*c->pool, (size_t)nslots + 1, &ipos));
-                    OKM_TRY(pool_get(*c->pool, scan_tmp_elems(nslots + 1), &itmp));
-                    for (void *p : {(void *)d_items, (void *)iflags, (void *)ipos, (void *)itmp}) level_bufs.push_back(p);
+                    OKM_TRY(items.get(nslots, &dense_items));
+                    OKM_TRY(level.get((size_t)nslots + 1, &iflags));
+                    OKM_TRY(level.get((size_t)nslots + 1, &ipos));
+                    OKM_TRY(level.get(scan_tmp_elems(nslots + 1), &itmp));
                     launch_item_compact(c->stream, d_items, nslots, dense_items, iflags, ipos, itmp);
                     HIP_TRY(hipGetLastError());
+                    items.disown(d_items);  // the slot array dies with the level arrays from here
+                    level.own(d_items);
                     d_items = dense_items;
                     d_nitems = ipos + nslots;
                 }
@@ -2606,14 +2609,13 @@ static okm_status count_parts(okm_ctx *c, std::vector<DevSeg> &segtab, std::vect
                 // every item lies in the level arrays: the runs are not read again
                 // every item is one child in a level array (lk, or fk after the
                 // fan-out): its sorted run is staged in place, over its keys
-                OKM_TRY(count_and_compact(c, d_items, d_segs, nslots, L.total, L.total, weighted, level_bufs, flags,
+                OKM_TRY(count_and_compact(c, d_items, d_segs, nslots, L.total, L.total, weighted, level, items, flags,
                                           hf, &aborted, d_nitems, dst, true, true));
                 if (!aborted) {
                     c->info.max_partition = hf[2];
                     return OKM_OK;
                 }
-                c->pool->put(d_items);
-                c->pool->put(d_segs);
+                items.free_all();  // (the level arrays stay: the host rounds read them)
                 d_items = nullptr;
                 d_segs = nullptr;
                 if (hf[1] & 1) {  // a child outgrew its sampled slot: redo the pass exactly
@@ -2642,14 +2644,14 @@ static okm_status count_parts(okm_ctx *c, std::vector<DevSeg> &segtab, std::vect
         }
         if (todo.empty()) break;
         Level L;
-        OKM_TRY(split_launch(c, segtab, parts, todo, bits, weighted, level_bufs, L));
+        OKM_TRY(split_launch(c, segtab, parts, todo, bits, weighted, level, L));
         OKM_TRY(split_children_host(c, L, segtab, parts, todo, bits));
     }
 
     // items on the host view: the parts themselves
-    std::vector<DevItem> items;
+    std::vector<DevItem> host_items;
     nitems = (uint32_t)parts.size();
-    items.resize(nitems);
+    host_items.resize(nitems);
     bool one_seg = true;  // every part one child in a level array: its run is staged in place
     for (uint32_t i = 0; i < nitems; ++i) {
         one_seg &= parts[i].seg_count == 1;
@@ -2657,7 +2659,7 @@ static okm_status count_parts(okm_ctx *c, std::vector<DevSeg> &segtab, std::vect
         const uint32_t rem = twok - parts[i].consumed;
         const uint64_t bound = rem >= 63 ? parts[i].len : std::min<uint64_t>(parts[i].len, 1ull << rem);
         const DevSeg &s0 = segtab[parts[i].seg_begin];
-        items[i] = DevItem{parts[i].seg_begin, parts[i].seg_count, out_total, rem, 0, parts[i].len, s0.keys, s0.counts};
+        host_items[i] = DevItem{parts[i].seg_begin, parts[i].seg_count, out_total, rem, 0, parts[i].len, s0.keys, s0.counts};
         out_total += bound;
         in_total += parts[i].len;
         c->info.max_partition = std::max(c->info.max_partition, parts[i].len);
@@ -2665,21 +2667,21 @@ static okm_status count_parts(okm_ctx *c, std::vector<DevSeg> &segtab, std::vect
     }
     c->info.work_items = nitems;
     if (nitems == 0) {
-        for (void *p : level_bufs) c->pool->put(p);
+        level.free_all();
         c->counted = true;
         c->n_res = 0;
         c->info.distinct = 0;
         return OKM_OK;
     }
-    OKM_TRY(pool_get(*c->pool, segtab.size(), &d_segs));
-    OKM_TRY(pool_get(*c->pool, nitems, &d_items));
+    OKM_TRY(items.get(segtab.size(), &d_segs));
+    OKM_TRY(items.get(nitems, &d_items));
     OKM_TRY(h2d(c, d_segs, segtab.data(), segtab.size() * sizeof(DevSeg)));
-    OKM_TRY(h2d(c, d_items, items.data(), nitems * sizeof(DevItem)));
+    OKM_TRY(h2d(c, d_items, host_items.data(), nitems * sizeof(DevItem)));
     c->hprof.mark("items.build");
     // (parts that never took part in a split round keep their run segments:
     // those are staged in a separate array)
-    return count_and_compact(c, d_items, d_segs, nitems, out_total, in_total, weighted, level_bufs, nullptr, nullptr,
-                             nullptr, nullptr, dst, false, one_seg && !level_bufs.empty());
+    return count_and_compact(c, d_items, d_segs, nitems, out_total, in_total, weighted, level, items, nullptr, nullptr,
+                             nullptr, nullptr, dst, false, one_seg && !level.held().empty());
 }
 
 // Memory-bounded counting.  The working set of a count (level array, fan-out
@@ -2801,41 +2803,18 @@ static okm_status count_grouped(okm_ctx *c, std::vector<DevSeg> &segtab, std::ve
         uint64_t *keys, *counts, n;
     };
     std::vector<Tab> tabs;
-    // every table block goes back to the pool on any error path (a stranded
-    // block would make the caller's retry run out of memory sooner)
-    struct Guard {
-        okm_ctx *c;
-        ResDst *d;
-        std::vector<Tab> *tabs;
-        bool armed = true;
-        bool keys_are_run = false;  // (the run's block: it stays with the run)
-        ~Guard() {
-            if (!armed) return;
-            if (!keys_are_run) c->pool->put(d->keys);
-            c->pool->put(d->counts);
-            for (auto &t : *tabs) {
-                c->pool->put(t.keys);
-                c->pool->put(t.counts);
-            }
-        }
-    } guard{c, &d, &tabs};
+    // the bound table (mode 1) or the groups' exact tables (mode 2), and the
+    // pipelined groups' device word
+    Blocks tables(*c->pool);
     if (mode == 1) {
-        if (over) {
-            d.keys = over->keys;
-            guard.keys_are_run = true;
-        } else {
-            OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(total, 1) * c->kw, &d.keys));
-        }
-        OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(total, 1), &d.counts));
+        if (over)
+            d.keys = over->keys;  // (the run's block: it stays the run's until the table is published)
+        else
+            OKM_TRY(tables.get(std::max<uint64_t>(total, 1) * c->kw, &d.keys));
+        OKM_TRY(tables.get(std::max<uint64_t>(total, 1), &d.counts));
     }
     // once a group wrote over the run, a failure leaves no input to count again
-    struct Lost {
-        okm_ctx *c;
-        bool on = false;
-        ~Lost() {
-            if (on) c->input_lost = true;
-        }
-    } lost{c};
+    Lost lost{c};
     const okm_engine_info info0 = c->info;
     okm_engine_info agg = info0;
     agg.work_items = 0;
@@ -2858,20 +2837,13 @@ static okm_status count_grouped(okm_ctx *c, std::vector<DevSeg> &segtab, std::ve
     // the groups from the first abandoned one on are counted again, one sync
     // each, from the base the groups before it reached (their entries are in
     // place, and the runs of the groups from there on are intact).
-    struct Slots {
-        okm_ctx *c;
-        unsigned long long *p = nullptr, *d_base = nullptr;
-        ~Slots() {
-            host_pinned_free(p);
-            c->pool->put(d_base);
-        }
-    } slots{c};
-    unsigned long long *&d_base = slots.d_base;
+    std::unique_ptr<unsigned long long, void (*)(void *)> slots(nullptr, host_pinned_free);  // page-locked
+    unsigned long long *d_base = nullptr;
     const size_t G = cuts.size() - 1;
     bool pipelined = mode == 1 && G > 1;
     if (pipelined) {
-        slots.p = static_cast<unsigned long long *>(host_pinned_alloc(G * 8 * sizeof(unsigned long long)));
-        pipelined = slots.p && pool_get(*c->pool, 1, &d_base) == OKM_OK;
+        slots.reset(static_cast<unsigned long long *>(host_pinned_alloc(G * 8 * sizeof(unsigned long long))));
+        pipelined = slots && tables.get(1, &d_base) == OKM_OK;
         if (pipelined) HIP_TRY(hipMemsetAsync(d_base, 0, sizeof(unsigned long long), c->stream));
     }
     size_t g_from = 0;  // the first group of this pass
@@ -2889,7 +2861,7 @@ static okm_status count_grouped(okm_ctx *c, std::vector<DevSeg> &segtab, std::ve
             std::vector<Part> sub(parts.begin() + cuts[g], parts.begin() + cuts[g + 1]);
             c->info.levels = 0;
             c->info.l2_bits = 0;
-            if (pipelined) d.hslot = slots.p + 8 * g;
+            if (pipelined) d.hslot = slots.get() + 8 * g;
             OKM_TRY(count_parts(c, segtab, sub, weighted, cp, mode == 1 ? &d : nullptr));
             lost.on = over != nullptr;  // (this group's keys are written, or queued)
             agg.levels = std::max(agg.levels, c->info.levels);
@@ -2904,6 +2876,8 @@ static okm_status count_grouped(okm_ctx *c, std::vector<DevSeg> &segtab, std::ve
                 OKM_TRY(ensure_dense(c));
                 OKM_TRY(shrink_table(c, &c->res_keys, &c->res_counts, c->n_res, 1.0));
                 tabs.push_back(Tab{c->res_keys, c->res_counts, c->n_res});
+                tables.own(c->res_keys);  // the group's table leaves the result
+                tables.own(c->res_counts);
                 c->res_keys = c->res_counts = nullptr;
             }
             ++ngroups;
@@ -2916,7 +2890,7 @@ static okm_status count_grouped(okm_ctx *c, std::vector<DevSeg> &segtab, std::ve
         base = c->hres[kHresCount];
         size_t first_bad = G;
         for (size_t g = 0; g < G; ++g) {
-            const unsigned long long *hs = slots.p + 8 * g;
+            const unsigned long long *hs = slots.get() + 8 * g;
             if (hs[1]) return fail(OKM_E_DEVICE, "count_items invariant violated (code " + std::to_string(hs[1]) + ")");
             if ((hs[2] | hs[3]) != 0 && first_bad == G) first_bad = g;
             agg.max_partition = std::max<uint64_t>(agg.max_partition, hs[4]);
@@ -2934,7 +2908,8 @@ static okm_status count_grouped(okm_ctx *c, std::vector<DevSeg> &segtab, std::ve
     lost.on = false;
     uint64_t nd = d.off;
     if (mode == 1) {
-        guard.armed = false;
+        tables.disown(d.keys);  // published: the result owns the table from here
+        tables.disown(d.counts);
         c->res_keys = d.keys;
         c->res_counts = d.counts;
         if (over) {  // the run's block is the table's now; the run is gone (released after the count)
@@ -2949,8 +2924,7 @@ static okm_status count_grouped(okm_ctx *c, std::vector<DevSeg> &segtab, std::ve
     } else {
         nd = 0;
         for (auto &t : tabs) nd += t.n;
-        OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(nd, 1) * c->kw, &c->res_keys));
-        OKM_TRY(pool_get(*c->pool, std::max<uint64_t>(nd, 1), &c->res_counts));
+        OKM_TRY(get_result(c, nd));
         uint64_t o = 0;
         for (auto &t : tabs) {
             if (t.n) {
@@ -2960,8 +2934,9 @@ static okm_status count_grouped(okm_ctx *c, std::vector<DevSeg> &segtab, std::ve
             }
             o += t.n;
         }
-        OKM_TRY(sync(c));  // the guard returns the groups' tables (and only them: d is unused in mode 2)
+        OKM_TRY(sync(c));
     }
+    tables.free_all();  // the groups' tables (mode 2), the pipelined groups' word
     agg.distinct = nd;
     agg.groups = ngroups;
     c->info = agg;
@@ -3319,13 +3294,13 @@ okm_status okm_add_pairs(okm_ctx *c, const uint64_t *keys, const uint64_t *count
     if (!keys) return fail(OKM_E_ARG, "okm_add_pairs: null keys");
     HIP_TRY(hipSetDevice(c->device));
     uint64_t *dk = nullptr, *dc = nullptr;
-    OKM_TRY(pool_get(*c->pool, n * c->kw, &dk));
-    if (counts) OKM_TRY(pool_get(*c->pool, n, &dc));
+    Blocks upload(*c->pool);
+    OKM_TRY(upload.get(n * c->kw, &dk));
+    if (counts) OKM_TRY(upload.get(n, &dc));
     HIP_TRY(hipMemcpyAsync(dk, keys, n * 8 * c->kw, hipMemcpyHostToDevice, c->stream));
     if (counts) HIP_TRY(hipMemcpyAsync(dc, counts, n * 8, hipMemcpyHostToDevice, c->stream));
     okm_status s = okm_add_pairs_device(c, dk, dc, n);
-    c->pool->put(dk);
-    c->pool->put(dc);
+    upload.free_all();
     return s;
 }
 
@@ -3342,20 +3317,21 @@ static okm_status result_to_device(okm_ctx *c) {
     if (!c->res_host) return OKM_OK;
     const uint64_t n = c->n_res;
     uint64_t *dk = nullptr, *dc = nullptr;
-    okm_status st = pool_get(*c->pool, std::max<uint64_t>(n, 1) * c->kw, &dk);
-    if (st == OKM_OK) st = pool_get(*c->pool, std::max<uint64_t>(n, 1), &dc);
-    if (st != OKM_OK) {
-        c->pool->put(dk);
+    Blocks own(*c->pool);
+    okm_status st = own.get(std::max<uint64_t>(n, 1) * c->kw, &dk);
+    if (st == OKM_OK) st = own.get(std::max<uint64_t>(n, 1), &dc);
+    if (st != OKM_OK)
         return fail(OKM_E_NOMEM, "the counted table (" + std::to_string(n) +
                                      " entries) lies in host memory and does not fit on the device: read it with "
                                      "okm_fetch_counts / okm_finish_counts");
-    }
     if (n) {
         HIP_TRY(hipMemcpyAsync(dk, c->res_keys, n * 8 * c->kw, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(dc, c->res_counts, n * 8, hipMemcpyHostToDevice, c->stream));
     }
     OKM_TRY(sync(c));
     host_table_free(c, c->res_keys, c->res_counts, n);
+    own.disown(dk);  // published: the result owns both from here
+    own.disown(dc);
     c->res_keys = dk;
     c->res_counts = dc;
     c->res_host = false;
@@ -3384,12 +3360,13 @@ static okm_status fetch_range(okm_ctx *c, const uint64_t *dk, const uint64_t *dc
     const uint64_t *src_k = dk, *src_c = dc;
     uint64_t cnt = n;
     uint64_t *tk = nullptr, *tc = nullptr;
+    Blocks scan(*c->pool), kept(*c->pool);  // the filter's block counts; the entries it keeps
     if (min_count > 1) {
         const uint32_t nb = filter_blocks(n);
         unsigned long long *bc, *bo, *tmp;
-        OKM_TRY(pool_get(*c->pool, nb + 1, &bc));
-        OKM_TRY(pool_get(*c->pool, nb + 1, &bo));
-        OKM_TRY(pool_get(*c->pool, scan_tmp_elems(nb + 1), &tmp));
+        OKM_TRY(scan.get(nb + 1, &bc));
+        OKM_TRY(scan.get(nb + 1, &bo));
+        OKM_TRY(scan.get(scan_tmp_elems(nb + 1), &tmp));
         HIP_TRY(hipMemsetAsync(bc, 0, (nb + 1) * sizeof(unsigned long long), c->stream));
         launch_filter_count(c->stream, dc, n, min_count, bc, nb);
         launch_exclusive_scan(c->stream, bc, bo, nb + 1, tmp);
@@ -3397,17 +3374,14 @@ static okm_status fetch_range(okm_ctx *c, const uint64_t *dk, const uint64_t *dc
         HIP_TRY(hipMemcpyAsync(&tot, bo + nb, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
         OKM_TRY(sync(c));
         cnt = tot;
-        if ((keys || counts) && cnt > cap) {
-            c->pool->put(bc); c->pool->put(bo); c->pool->put(tmp);
-            return fail(OKM_E_OVERFLOW, "okm_fetch_counts: buffer too small");
-        }
+        if ((keys || counts) && cnt > cap) return fail(OKM_E_OVERFLOW, "okm_fetch_counts: buffer too small");
         if (cnt && (keys || counts)) {
-            OKM_TRY(pool_get(*c->pool, cnt * c->kw, &tk));
-            OKM_TRY(pool_get(*c->pool, cnt, &tc));
+            OKM_TRY(kept.get(cnt * c->kw, &tk));
+            OKM_TRY(kept.get(cnt, &tc));
             launch_filter_scatter(c->stream, dk, dc, n, min_count, bo, tk, tc, c->wide);
             HIP_TRY(hipGetLastError());
         }
-        c->pool->put(bc); c->pool->put(bo); c->pool->put(tmp);
+        scan.free_all();
         src_k = tk;
         src_c = tc;
     } else if ((keys || counts) && cnt > cap) {
@@ -3419,8 +3393,7 @@ static okm_status fetch_range(okm_ctx *c, const uint64_t *dk, const uint64_t *dc
         if (counts) HIP_TRY(hipMemcpyAsync(counts, src_c, cnt * 8, kind, c->stream));
         OKM_TRY(sync(c));
     }
-    if (tk) c->pool->put(tk);
-    if (tc) c->pool->put(tc);
+    kept.free_all();
     *m = cnt;
     return OKM_OK;
 }
@@ -3437,8 +3410,9 @@ static okm_status fetch_result(okm_ctx *c, uint64_t min_count, uint64_t *keys, u
     constexpr uint64_t kSlice = uint64_t(1) << 26;
     const uint64_t sl = std::min<uint64_t>(kSlice, c->n_res);
     uint64_t *dk = nullptr, *dc = nullptr;
-    OKM_TRY(pool_get(*c->pool, sl * c->kw, &dk));
-    okm_status st = pool_get(*c->pool, sl, &dc);
+    Blocks slice(*c->pool);
+    OKM_TRY(slice.get(sl * c->kw, &dk));
+    okm_status st = slice.get(sl, &dc);
     uint64_t done = 0;
     for (uint64_t o = 0; o < c->n_res && st == OKM_OK; o += sl) {
         const uint64_t len = std::min(sl, c->n_res - o);
@@ -3454,8 +3428,7 @@ static okm_status fetch_result(okm_ctx *c, uint64_t min_count, uint64_t *keys, u
                          out && counts ? counts + done : nullptr, out ? cap - done : 0, &got, dst_on_device);
         done += got;
     }
-    c->pool->put(dk);
-    c->pool->put(dc);
+    slice.free_all();
     OKM_TRY(st);
     *n = done;
     return OKM_OK;
@@ -3625,6 +3598,8 @@ okm_status okm_engine_info_get(okm_ctx *c, okm_engine_info *info) {
     info->spills = c->spills;
     return OKM_OK;
 }
+
+uint64_t okm_test_device_in_use(okm_ctx *c) { return c ? c->pool->in_use() : 0; }
 
 okm_status okm_device_alloc(int device, uint64_t bytes, void **d_ptr) {
     if (!d_ptr) return fail(OKM_E_ARG, "null out");

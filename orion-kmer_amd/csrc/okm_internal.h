@@ -26,6 +26,8 @@ void host_pinned_free(void *p);
 okm_status memcpy_d2h_on(int device, void *dst, const void *src, size_t bytes);
 // Test hook value (orion_kmer_testing.h okm_test_knob), -1 when unset.
 int64_t test_knob(int knob);
+// OKM_TEST_FAIL_ALLOC: counts one device arena allocation; true for the one that is to fail.
+bool test_fail_alloc();
 
 // Give back the idle device memory every context's pool on `device` caches
 // (a hipMalloc outside the pools, e.g. a communicator buffer, retries after it).

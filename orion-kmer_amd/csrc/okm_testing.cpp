@@ -18,6 +18,14 @@ struct Init {
 int64_t test_knob(int knob) {
     return knob >= 0 && knob < OKM_TEST_KNOBS ? g_knobs[knob].load(std::memory_order_relaxed) : -1;
 }
+
+bool test_fail_alloc() {
+    std::atomic<int64_t> &k = g_knobs[OKM_TEST_FAIL_ALLOC];
+    int64_t v = k.load(std::memory_order_relaxed);
+    while (v > 0)
+        if (k.compare_exchange_weak(v, v == 1 ? -1 : v - 1)) return v == 1;
+    return false;
+}
 }  // namespace okm
 
 extern "C" {

@@ -174,6 +174,7 @@ PROTOTYPES = {
                                        c_double, c_void_p, c_int]),
     "okm_test_set": (None, [c_int, c_int64]),
     "okm_test_get": (c_int64, [c_int]),
+    "okm_test_device_in_use": (c_uint64, [c_void_p]),
     "okm_synth_long_reads": (c_int, [c_uint64, c_uint64, c_uint64, c_uint64, c_uint64, c_double, c_double, c_uint32,
                                      c_uint32, c_double, c_double, c_double, POINTER(c_void_p), _P64, c_void_p,
                                      c_int]),

@@ -29,6 +29,7 @@ KNOBS: Dict[str, int] = {
     "hbm_budget_bytes": 15,
     "group_over": 16,
     "l1_max_blocks": 17,
+    "fail_alloc": 18,
 }
 
 
@@ -39,6 +40,11 @@ def set_knob(name: str, value: int) -> None:
 
 def get_knob(name: str) -> int:
     return int(_lib.load().okm_test_get(KNOBS[name]))
+
+
+def device_in_use(counter) -> int:
+    """Bytes of the counter's device arena that are allocated right now."""
+    return int(_lib.load().okm_test_device_in_use(counter.ctx))
 
 
 def reset_all() -> None:
