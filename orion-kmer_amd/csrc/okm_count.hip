@@ -32,7 +32,9 @@
 
 namespace okm {
 
-constexpr int kCountWpe = 8;  // waves per EU floor of the unweighted tag kernel: 4 blocks/CU (64 VGPRs)
+// waves per EU floor of the unweighted tag kernel: 4 blocks/CU (64 VGPRs).  6 (70
+// VGPRs, 3 blocks/CU) measured 1.56 against 1.34 ms on C2 (profiles/AB_LOG.md)
+constexpr int kCountWpe = 8;
 constexpr int kFullHomeBitsW = 12;  // full mode, K128 keys: 4096 homes (~1 key each at 4096 instances)
 
 // Threads per counting workgroup: 512, 4096-instance items (256 threads and
@@ -80,18 +82,9 @@ struct CountType<true> {
     typedef ull T;
 };
 
-__device__ __forceinline__ uint32_t wave_incl_scan32(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
-// Block-wide exclusive scan (u32); returns the block total in *total.  Two
-// barriers (LDS-only ones when LDS_ONLY: see lds_only_sync).
+// Block-wide exclusive scan (u32; the wave step is okm_dev_common.h's DPP
+// scan); returns the block total in *total.  Two barriers (LDS-only ones when
+// LDS_ONLY: see lds_only_sync).
 __device__ __forceinline__ void lds_only_sync();
 template <bool LDS_ONLY = false>
 __device__ __forceinline__ uint32_t block_excl_scan32(uint32_t v, uint32_t *wsum, uint32_t *total) {
@@ -223,6 +216,32 @@ __device__ __forceinline__ void load_item(const DevItem &it, const DevSeg *__res
         }
         sbase += len;
     }
+}
+
+// A single-segment item's keys, straight from the item's own pointer (the
+// unweighted batch path: k_make_items and the fan-out only make such items).
+// Every row is a load masked by its lanes' own bound, with no block-uniform
+// exit between the rows: a wave whose lanes are all past the end skips its
+// load, and the rows stay eight independent values.  (With an exit after the
+// last row in use, as in load_item, the compiler merges the rows as one
+// 16-register tuple and copies it at every exit; rows left unset instead are
+// carried from item to item, 16 more live registers and spills.)
+__device__ __forceinline__ void load_item_one(const uint64_t *__restrict__ keys, uint32_t len, ull (&kk)[kPer]) {
+    const uint32_t t = threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+        const uint32_t f = (uint32_t)u * kCB + t;
+        kk[u] = kEmptyKey;
+        if (f < len) kk[u] = gload(reinterpret_cast<const ull *>(keys) + f);
+    }
+}
+
+// Stores at a 32-bit index from a block-uniform global base: the address is
+// the scalar base plus a 32-bit byte offset (no 64-bit VALU add per key).
+typedef __attribute__((address_space(1))) char gchar;
+template <typename T>
+__device__ __forceinline__ void gstore_at(gchar *base, uint32_t idx, T v) {
+    *reinterpret_cast<__attribute__((address_space(1))) T *>(base + idx * (uint32_t)sizeof(T)) = v;
 }
 
 // A multi-segment item (sorted runs: every run's slice of one key range) with
@@ -579,14 +598,14 @@ __device__ __forceinline__ uint32_t full_item(const DevItem &it, uint32_t nrows,
 
 constexpr uint32_t kDeferred = ~0u;
 
+// ip: the item in the item array; its output slot (out_off, keys0) is read in
+// step 6, where it is used, so that it is not held in registers through the
+// steps before.  ww: the rows' weights (weighted launches only).
 template <bool W, bool NW = false>
-__device__ __forceinline__ uint32_t tag_item(const DevItem &it, const DevSeg *__restrict__ segs, uint32_t nrows,
-                                             const ull (&kk)[kPer], const ull (&ww)[kPer], ull *lds, uint32_t *wsum,
-                                             uint64_t *__restrict__ out_keys, uint64_t *__restrict__ out_counts,
-                                             bool narrow, ull *ctl) {
-    const uint32_t r = it.rem_bits;
-    const uint64_t out_off = it.out_off;
-    ull *okeys = out_slot_keys<ull>(it, out_keys);
+__device__ __forceinline__ uint32_t tag_item(const DevItem *__restrict__ ip, uint32_t r, uint32_t nrows,
+                                             const ull (&kk)[kPer], const ull (&ww)[W ? kPer : 1], ull *lds,
+                                             uint32_t *wsum, uint64_t *__restrict__ out_keys,
+                                             uint64_t *__restrict__ out_counts, bool narrow, ull *ctl) {
     typedef Lds<W> L;
     typedef typename CountType<W>::T CT;
     const uint32_t t = threadIdx.x;
@@ -606,16 +625,17 @@ __device__ __forceinline__ uint32_t tag_item(const DevItem &it, const DevSeg *__
     //    slower, 1.66 -> 1.71-1.78 ms on C2 at 2 / 4 rows per batch)
     uint32_t hp[kPer];  // rest: home << 16 | pos; otherwise ~0
 #pragma unroll
+    for (int u = 0; u < kPer; ++u) hp[u] = ~0u;
+#pragma unroll
     for (int u = 0; u < kPer; ++u) {
         if ((uint32_t)u >= nrows) break;  // block-uniform
-        hp[u] = ~0u;
         const ull x = kk[u];
         if (x != kEmptyKey) {
             const uint32_t h = home_of(x, r);
             const ull old = atomicCAS(&tag[h], kEmptyKey, x);
             if (old == kEmptyKey || old == x) {  // DashMap entry().or_insert().fetch_add() (count.rs:31-34)
                 if (W)
-                    atomicAdd(&tc64[h], ww[u]);
+                    atomicAdd(&tc64[h], ww[W ? u : 0]);
                 else
                     atomicAdd(&tc16[h >> 1], 1u << half_shift(h));  // <= 4096 per item: no carry
             } else {
@@ -651,7 +671,7 @@ __device__ __forceinline__ uint32_t tag_item(const DevItem &it, const DevSeg *__
             const uint32_t h = hp[u] >> 16;
             const uint32_t dst = half_of(rc[h >> 1], h) + (hp[u] & 0xFFFFu);
             rk[dst] = kk[u];
-            if (W) rw[dst] = ww[u];
+            if (W) rw[dst] = ww[W ? u : 0];
         }
     }
     lds_sync();
@@ -734,6 +754,23 @@ __device__ __forceinline__ uint32_t tag_item(const DevItem &it, const DevSeg *__
         hd[2 * t + 1] = ho[2] | (ho[3] << 16);
     }
     lds_sync();
+    if (NW) return __builtin_amdgcn_readfirstlane(D);
+    // the item's slot of the staged keys and counts (out_slot_keys: its own
+    // keys when in place), as block-uniform bases indexed by the 32-bit rank
+    const uint64_t out_off = ip->out_off;
+    // (every such pointer is a device allocation: see gload)
+    gchar *const okeys = out_keys ? (gchar *)(out_keys + out_off) : (gchar *)ip->keys0;
+    const bool c64 = W && !narrow;  // u64 counts (store_count)
+    gchar *const ocnt = (gchar *)out_counts + out_off * (c64 ? 8u : 4u);
+    auto put = [&](uint32_t o, ull key, uint64_t c) {
+        gstore_at<ull>(okeys, o, key);
+        if (c64) {
+            gstore_at<ull>(ocnt, o, c);
+        } else {
+            if (W && c > 0xFFFFFFFFull) atomicOr(reinterpret_cast<unsigned int *>(ctl), 8u);
+            gstore_at<uint32_t>(ocnt, o, (uint32_t)c);
+        }
+    };
     // 6a. tags: rank = home offset + rest distinct keys below the tag
     {
         const uint32_t lq[kHomesPer] = {lw0 & 0xFFFFu, lw0 >> 16, lw1 & 0xFFFFu, lw1 >> 16};
@@ -746,18 +783,13 @@ __device__ __forceinline__ uint32_t tag_item(const DevItem &it, const DevSeg *__
         }
 #pragma unroll
         for (int q = 0; q < kHomesPer; ++q) {
-            if (!NW && tg[q] != kEmptyKey) {
-                const uint64_t o = out_off + ho[q] + lq[q];
-                okeys[o - out_off] = tg[q];
-                const uint64_t cq = W ? (uint64_t)tw[q] : (uint64_t)nq[q];
-                store_count<W>(out_counts, o, cq, narrow, ctl);
-            }
+            if (tg[q] != kEmptyKey) put(ho[q] + lq[q], tg[q], W ? (uint64_t)tw[W ? q : 0] : (uint64_t)nq[q]);
         }
     }
     // 6b. rest keys: rank = home offset + rest distinct keys below + [tag below]
 #pragma unroll
     for (int k = 0; k < L::kRestIters; ++k) {
-        if (NW || (uint32_t)k * kCB >= rtot) break;
+        if ((uint32_t)k * kCB >= rtot) break;
         if (prange[k]) {
             const ull x = px[k];
             const uint32_t hs = (prange[k] >> 16) & 0x7FFFu, he = prange[k] & 0xFFFFu;
@@ -765,9 +797,7 @@ __device__ __forceinline__ uint32_t tag_item(const DevItem &it, const DevSeg *__
             for (uint32_t q = hs; q < he; ++q) less += (rf[q] && rk[q] < x) ? 1u : 0u;
             const uint32_t h = home_of(x, r);
             const uint32_t tag_below = prange[k] >> 31;
-            const uint64_t o = out_off + half_of(hd[h >> 1], h) + less + tag_below;
-            okeys[o - out_off] = x;
-            store_count<W>(out_counts, o, (uint64_t)pc[k], narrow, ctl);
+            put(half_of(hd[h >> 1], h) + less + tag_below, x, (uint64_t)pc[k]);
         }
     }
     // late reset: everything but the home offsets (hd, cleared in the next
@@ -856,7 +886,12 @@ __device__ __forceinline__ uint32_t dense_item(const DevItem &it, const DevSeg *
 // after it: separate kernels keep the rare paths' registers out of this one.
 // NW (weighted launches only): count each item's distinct keys into n_out and
 // write nothing -- the first pass of an exact-size two-pass count.
-template <bool W, bool NW = false, bool NARROW = !W>
+// SEG1 (unweighted launches only): every item is expected to be one segment
+// (the batch path: k_make_items, the fan-out, single-run parts), loaded
+// straight from the item's key pointer; the multi-segment loaders and their
+// merges stay out of the kernel, and an item of several segments that turns up
+// anyway is deferred to k_count_slow like any other item it cannot take.
+template <bool W, bool NW = false, bool NARROW = !W, bool SEG1 = false>
 __global__ __launch_bounds__(kCB) __attribute__((amdgpu_waves_per_eu(W ? 1 : kCountWpe)))
 void k_count_items(const DevItem *__restrict__ items, uint32_t nitems, const DevSeg *__restrict__ segs,
                    uint64_t *__restrict__ out_keys, uint64_t *__restrict__ out_counts, ull *__restrict__ n_out,
@@ -877,8 +912,36 @@ void k_count_items(const DevItem *__restrict__ items, uint32_t nitems, const Dev
     tag_reset<W>(lds);
     // Block-uniform values that steer code containing barriers come from
     // blockIdx / scalar loads (see DESIGN.md on the structuriser).
+    static_assert(!(SEG1 && W), "the single-segment kernel is the unweighted one");
     for (uint32_t item = blockIdx.x; item < nitems; item += gridDim.x) {
-        const DevItem it = items[item];
+        const DevItem *ip = items + item;
+        if (SEG1) {
+            // the item's fields are read where they are used (the output slot in
+            // tag_item's step 6), not held across the item
+            const uint64_t total = ip->pad == kItemEmpty ? 0 : ip->total;
+            if (total == 0) {  // an empty fan-out slot (block-uniform)
+                if (t == 0) n_out[item] = 0;
+                continue;
+            }
+            uint32_t written = kDeferred;
+            const uint32_t r = ip->rem_bits;
+            if (r > (uint32_t)kDenseBits && total <= (uint64_t)kCapI && ip->seg_count == 1) {
+                const uint32_t len = (uint32_t)total;
+                const uint32_t nrows = (len + kCB - 1) / kCB;  // rows of kk in use (block-uniform)
+                ull kk[kPer];
+                const ull none[1] = {1};
+                load_item_one(ip->keys0, len, kk);
+                written = tag_item<false, NW>(ip, r, nrows, kk, none, lds, wsum, out_keys, out_counts, NARROW, ctl);
+            }
+            if (t == 0) {
+                if (written == kDeferred)
+                    defer[atomicAdd(reinterpret_cast<unsigned int *>(ctl + 1), 1u)] = item;
+                else
+                    n_out[item] = written;
+            }
+            continue;
+        }
+        const DevItem it = *ip;
         const uint64_t total = it.pad == kItemEmpty ? 0 : item_total(it, segs);
         if (total == 0) {  // an empty fan-out slot (block-uniform)
             if (t == 0) n_out[item] = 0;
@@ -895,7 +958,12 @@ void k_count_items(const DevItem *__restrict__ items, uint32_t nitems, const Dev
             else
                 load_item<W>(it, segs, kk, ww);
             const uint32_t nrows = (uint32_t)((total + kCB - 1) / kCB);  // rows of kk in use (block-uniform)
-            written = tag_item<W, NW>(it, segs, nrows, kk, ww, lds, wsum, out_keys, out_counts, NARROW, ctl);
+            if constexpr (W) {
+                written = tag_item<W, NW>(ip, it.rem_bits, nrows, kk, ww, lds, wsum, out_keys, out_counts, NARROW, ctl);
+            } else {
+                const ull none[1] = {1};
+                written = tag_item<W, NW>(ip, it.rem_bits, nrows, kk, none, lds, wsum, out_keys, out_counts, NARROW, ctl);
+            }
         }
         if (t == 0) {
             if (written == kDeferred)
@@ -989,7 +1057,7 @@ void launch_count_items(void *stream, const DevItem *items, uint32_t nitems, con
                         uint64_t *out_keys, uint64_t *out_counts, unsigned long long *n_out,
                         unsigned long long *ctl, uint32_t *defer, bool weighted, bool wide,
                         const unsigned long long *guard, const unsigned long long *d_nitems, bool nowrite,
-                        bool narrow) {
+                        bool narrow, bool multi_seg) {
     if (!nitems) return;
     hipStream_t s = (hipStream_t)stream;
     // wide (full-mode) count: 8191 workgroups against 4095, k=63 at 1 Gbases
@@ -1031,8 +1099,14 @@ void launch_count_items(void *stream, const DevItem *items, uint32_t nitems, con
                            out_counts, n_out, ctl, (const uint32_t *)defer, guard, d_nitems, nowrite, narrow,
                            (ull *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, (const ull *)nullptr);
     } else {
-        hipLaunchKernelGGL(k_count_items<false>, dim3(grid), dim3(kCB), 0, s, items, nitems, segs, out_keys,
-                           out_counts, n_out, ctl, defer, guard, d_nitems);
+        // multi_seg: some item may span several segments (sorted runs, parts
+        // that kept their run segments); else the single-segment kernel
+        if (multi_seg)
+            hipLaunchKernelGGL(k_count_items<false>, dim3(grid), dim3(kCB), 0, s, items, nitems, segs, out_keys,
+                               out_counts, n_out, ctl, defer, guard, d_nitems);
+        else
+            hipLaunchKernelGGL((k_count_items<false, false, true, true>), dim3(grid), dim3(kCB), 0, s, items, nitems,
+                               segs, out_keys, out_counts, n_out, ctl, defer, guard, d_nitems);
         hipLaunchKernelGGL((k_count_slow<ull, false>), dim3(sgrid), dim3(kCB), 0, s, items, nitems, segs, out_keys,
                            out_counts, n_out, ctl, (const uint32_t *)defer, guard, d_nitems, nowrite, narrow,
                            (ull *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, (const ull *)nullptr);

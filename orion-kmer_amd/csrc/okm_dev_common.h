@@ -89,4 +89,40 @@ __device__ __forceinline__ ull block_excl_scan_1b(ull v, ull *wsum, ull *total) 
     return wbase + inc - v;
 }
 
+// Inclusive wave scan of a u32 in six DPP adds (row shifts by 1, 2, 4, 8
+// inside the rows of 16 lanes, then lane 15 of each row into the next row and
+// lane 31 into the upper half): no LDS permutes and no lane compares, unlike
+// the __shfl_up ladder above.  A lane whose source is off its row's edge, or
+// whose row the broadcast masks out, adds the `old` value 0.  All 64 lanes
+// must be active (the block scans below are block-uniform calls).
+__device__ __forceinline__ uint32_t wave_incl_scan32(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);  // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);  // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);  // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);  // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
+    return v;
+}
+
+// block_excl_scan / block_excl_scan_1b for values whose block sum fits 32 bits
+// (tile histograms: at most the tile's keys).  wsum: BLOCK/64 u32 LDS words.
+template <int BLOCK, bool TRAILING = true>
+__device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t v, uint32_t *wsum, uint32_t *total) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const uint32_t inc = wave_incl_scan32(v);
+    if (lane == 63) wsum[wid] = inc;
+    lds_sync();
+    uint32_t wbase = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < BLOCK / 64; ++w) {
+        const uint32_t s = wsum[w];
+        wbase += w < wid ? s : 0u;
+        tot += s;
+    }
+    if (TRAILING) lds_sync();
+    *total = tot;
+    return wbase + inc - v;
+}
+
 }  // namespace okm

@@ -1574,7 +1574,7 @@ static okm_status count_and_compact(okm_ctx *c, DevItem *d_items, DevSeg *d_segs
                                     Blocks &items, const unsigned long long *guard = nullptr,
                                     unsigned long long *hguard = nullptr, bool *aborted = nullptr,
                                     const unsigned long long *d_nitems = nullptr, const ResDst *dst = nullptr,
-                                    bool last_use = false, bool in_place = false) {
+                                    bool last_use = false, bool in_place = false, bool multi_seg = false) {
     uint64_t *sk = nullptr, *sc = nullptr;
     unsigned long long *n_out, *dense_off, *scan_tmp;
     // wide keys into a caller's table: the count kernel writes the table
@@ -1637,7 +1637,7 @@ static okm_status count_and_compact(okm_ctx *c, DevItem *d_items, DevSeg *d_segs
                             dst->d_base ? dst->counts : dst->counts + dst->off, dst->d_base);
     else
         launch_count_items(c->stream, d_items, nitems, d_segs, sk, sc, n_out, c->flag, defer, weighted, c->wide, guard,
-                           d_nitems, false, narrow);
+                           d_nitems, false, narrow, multi_seg);
     c->timer.end(c->stream, "count_items", (8.0 * c->kw + (weighted ? 8.0 : 0.0)) * (double)in_total);
     HIP_TRY(hipGetLastError());
     launch_exclusive_scan(c->stream, n_out, dense_off, nitems + 1, scan_tmp);
@@ -1707,7 +1707,7 @@ static okm_status count_and_compact(okm_ctx *c, DevItem *d_items, DevSeg *d_segs
         HIP_TRY(hipMemsetAsync(d_nitems ? n_out : n_out + nitems, 0,
                                (d_nitems ? nitems + 1 : 1) * sizeof(unsigned long long), c->stream));
         launch_count_items(c->stream, d_items, nitems, d_segs, sk, sc, n_out, c->flag, defer, weighted, c->wide, guard,
-                           d_nitems, false, false);
+                           d_nitems, false, false, multi_seg);
         HIP_TRY(hipGetLastError());
         launch_exclusive_scan(c->stream, n_out, dense_off, nitems + 1, scan_tmp);
         HIP_TRY(hipMemcpyAsync(&hv[0], dense_off + nitems, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -2147,7 +2147,8 @@ static okm_status count_sorted_plan(okm_ctx *c, bool *fallback, std::vector<uint
     const bool two_pass = weighted && (mkv == 2 || (tight && mkv != 1));
     const bool merge = (mkv == 1 || tight) && R <= merge_max_runs() && item_max <= merge_item_capacity();
     if (!two_pass && !merge)
-        return count_and_compact(c, d_items, d_segs, nitems, in_total, in_total, weighted, bufs, items);
+        return count_and_compact(c, d_items, d_segs, nitems, in_total, in_total, weighted, bufs, items, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, false, false, /*multi_seg=*/true);
     items.move_to(bufs);  // (these two free everything at one point)
     if (two_pass) return count_sorted_two_pass(c, d_items, d_segs, nitems, in_total, bufs);
     return merge_sorted_items(c, d_items, d_segs, nitems, in_total, weighted, bufs);
@@ -2681,7 +2682,7 @@ static okm_status count_parts(okm_ctx *c, std::vector<DevSeg> &segtab, std::vect
     // (parts that never took part in a split round keep their run segments:
     // those are staged in a separate array)
     return count_and_compact(c, d_items, d_segs, nitems, out_total, in_total, weighted, level, items, nullptr, nullptr,
-                             nullptr, nullptr, dst, false, one_seg && !level.held().empty());
+                             nullptr, nullptr, dst, false, one_seg && !level.held().empty(), !one_seg);
 }
 
 // Memory-bounded counting.  The working set of a count (level array, fan-out

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(kScatBlock) __attribute__((amdgpu_waves_per_eu(kSca
     __shared__ ull gcur[kMaxL1Bins];         // this block's next output index per bin
     __shared__ uint32_t hist[kMaxL1Bins + 1];
     __shared__ uint32_t lofs[kMaxL1Bins];    // tile-local start of each bin in `stage`
-    __shared__ ull wsum[kScatBlock / 64];
+    __shared__ uint32_t wsum[kScatBlock / 64];
     const uint32_t t = threadIdx.x;
     const uint32_t nb = g.nbins;
     // HC: exact per-block counts (one claim per bin for the whole chunk);
@@ -177,11 +177,9 @@ __global__ __launch_bounds__(kScatBlock) __attribute__((amdgpu_waves_per_eu(kSca
             lds_sync();
             hmine = t <= nb ? hist[t] : 0u;
             if (t <= nb) hist[t] = 0;
-            {
-                ull tn;
-                const uint32_t off = (uint32_t)block_excl_scan_1b<kScatBlock>(t < nb ? hmine : 0u, wsum, &tn);
+            {  // a tile's counts sum to at most kTile: a 32-bit scan
+                const uint32_t off = block_excl_scan_u32<kScatBlock, false>(t < nb ? hmine : 0u, wsum, &tile_n);
                 if (t < nb) lofs[t] = off;
-                tile_n = (uint32_t)tn;
             }
             // sampled capacities: issue this tile's claim now, consume it after the staging
             uint32_t ch = 0;

@@ -177,7 +177,11 @@ void launch_count_items(void *stream, const DevItem *items, uint32_t nitems, con
                         unsigned long long *ctl, uint32_t *defer, bool weighted, bool wide,
                         const unsigned long long *guard = nullptr, const unsigned long long *d_nitems = nullptr,
                         bool nowrite = false,  // nowrite: n_out only (weighted or wide launches)
-                        bool narrow = false);
+                        bool narrow = false,
+                        // multi_seg: some item may span several segments.  false (unweighted keys of
+                        // at most 64 bits): the single-segment tag kernel, which hands any other item
+                        // to the slow kernel -- exact either way, slower when such items are common
+                        bool multi_seg = false);
 // Wide keys straight into a caller's table (okm_count.hip: items by ticket,
 // each run at its look-back prefix; no staging, no compaction).  status:
 // nitems words and ctl[0..1] zeroed by the caller; fin_keys / fin_counts at

@@ -121,7 +121,7 @@ void k_part_scatter_tile(
     ull *gcur = W ? cstage + T : cstage;                                  // [max_local]
     uint32_t *hist = reinterpret_cast<uint32_t *>(gcur + max_local);      // [max_local]
     uint32_t *lofs = hist + max_local;                                    // [max_local]
-    __shared__ ull wsum[kPartBlock / 64];
+    __shared__ uint32_t wsum[kPartBlock / 64];
     KT *out_keys = reinterpret_cast<KT *>(out_keys_raw);
     const uint32_t t = threadIdx.x;
 
@@ -176,8 +176,8 @@ void k_part_scatter_tile(
                 claim[q] = 0;
                 if (!HC && my[q]) claim[q] = atomicAdd(&cursor[s.out_base + BPT * t + q], (ull)my[q]);
             }
-            ull tile_n;
-            uint32_t off = (uint32_t)block_excl_scan<kPartBlock>(mine, wsum, &tile_n);
+            uint32_t tile_n;  // at most the tile's T keys: a 32-bit scan
+            uint32_t off = block_excl_scan_u32<kPartBlock>(mine, wsum, &tile_n);
 #pragma unroll
             for (uint32_t q = 0; q < BPT; ++q) {
                 if (BPT * t + q < nl) lofs[BPT * t + q] = off;
@@ -209,7 +209,7 @@ void k_part_scatter_tile(
             }
             lds_sync();
             // each bin's run is contiguous in `stage` and in the output slice
-            for (uint32_t j = t; j < (uint32_t)tile_n; j += kPartBlock) {
+            for (uint32_t j = t; j < tile_n; j += kPartBlock) {
                 const KT key = stage[j];
                 const uint32_t b = local_bin(key, s);
                 const ull g = gcur[b];
