@@ -14,6 +14,12 @@ oracle, through the C ABI.
 - a BASELINE-size property: reads queried against the set of their own
   k-mers hit on every valid window (sum of hits == valid windows).
 Integer work: the bar is bit-exact (the two f64 divisions are the host's).
+
+The inputs here are large and random.  The edges they almost never reach
+(probes that wrap past the last slot, the ~0 flag through rehashes, the
+grid-stride loops past their caps, classify's walk over empty and tiny
+references, every k and unterminated batches in query) are aimed at on purpose
+in tests/test_gpu_probe_edges.py.
 """
 
 import gzip
