@@ -166,6 +166,24 @@ okm_status okm_finish_counts(okm_ctx *ctx, uint64_t min_count, uint64_t **keys, 
 okm_status okm_finish_set(okm_ctx *ctx, uint64_t **keys, uint64_t *n);
 void okm_free_result(void *p);
 
+/* The count histogram (abundance spectrum) of the counted table -- what
+ * jellyfish `histo` reports; an extension, the reference has none.  hist is
+ * HOST memory of n_bins entries, 2 <= n_bins <= 2^20 + 1: hist[0] = 0, hist[c]
+ * = distinct keys whose count is exactly c for 1 <= c < n_bins - 1, and
+ * hist[n_bins - 1] = keys with count >= n_bins - 1.  Counts first if batches
+ * are pending (as okm_result_size); an empty table gives zeros.  Read-only:
+ * the table stays where and as it lies (a count's per-item runs are not
+ * gathered, a host-resident table stays on the host and only its counts are
+ * uploaded, in slices), so every later reader behaves as if it had not been
+ * called.  A set-mode context has no counts: OKM_E_STATE. */
+typedef struct okm_count_summary {
+    uint64_t n_distinct;   /* entries of the table */
+    uint64_t n_instances;  /* sum of all counts, modulo 2^64 */
+    uint64_t max_count;    /* 0 for an empty table */
+} okm_count_summary;
+okm_status okm_count_histogram(okm_ctx *ctx, uint64_t *hist, uint64_t n_bins,
+                               okm_count_summary *summary /* may be NULL */);
+
 /* Device pointers to the counted, sorted, unfiltered table (valid until the
  * next add/reset/destroy). */
 okm_status okm_result_device(okm_ctx *ctx, const uint64_t **d_keys, const uint64_t **d_counts,
@@ -348,6 +366,10 @@ okm_status okm_group_finish_counts(okm_group *g, uint64_t min_count, uint64_t **
  * extension, utils.rs:167-198), streamed off the GPUs in chunks while the host
  * formats the previous one.  *n_lines (optional) = lines written. */
 okm_status okm_group_write_counts_tsv(okm_group *g, const char *path, uint64_t min_count, uint64_t *n_lines);
+/* okm_count_histogram over the group (counts first): the owners hold disjoint
+ * key ranges, so the histograms, n_distinct and n_instances add and max_count
+ * is the largest. */
+okm_status okm_group_count_histogram(okm_group *g, uint64_t *hist, uint64_t n_bins, okm_count_summary *summary);
 
 /* ------------------------------------------------------------------------
  * Instrumentation (bench.py measures kernels with HIP events on the
@@ -447,6 +469,10 @@ okm_status okm_parse_buffer(const uint8_t *data, uint64_t n, uint8_t **seq, uint
  * are okm_key128 pairs for k > 32). */
 okm_status okm_write_counts_tsv(const char *path, uint8_t k, const uint64_t *keys,
                                 const uint64_t *counts, uint64_t n);
+/* Writes an okm_count_histogram result as "COUNT\tKMERS\n" lines, ascending,
+ * bins holding zero omitted, no header; the last bin (every count >= n_bins -
+ * 1) goes under the label n_bins - 1, as jellyfish histo's high bin. */
+okm_status okm_write_histogram_tsv(const char *path, const uint64_t *hist, uint64_t n_bins);
 /* Writes `n` raw bytes through the extension-selected compressor. */
 okm_status okm_write_file(const char *path, const uint8_t *data, uint64_t n);
 /* Reads a whole file, decompressing by extension (utils.rs:125-152). */

@@ -73,7 +73,10 @@ typedef enum okm_test_knob {
      * bookkeeping, one allocation at a time.  A clean run under a huge n
      * tells how many allocations it made. */
     OKM_TEST_FAIL_ALLOC = 18,
-    OKM_TEST_KNOBS = 19
+    /* okm_count_histogram over a host-resident table: entries per uploaded
+     * slice of its counts instead of 2^26 */
+    OKM_TEST_HIST_SLICE = 19,
+    OKM_TEST_KNOBS = 20
 } okm_test_knob;
 
 /* value < 0 unsets the knob (the product default). */

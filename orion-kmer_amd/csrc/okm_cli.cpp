@@ -219,7 +219,7 @@ static const char *kVersion = "orion-kmer 0.1.0";
 
 static void print_help(const std::string &cmd) {
     if (cmd == "count")
-        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
+        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
     else if (cmd == "build")
         printf("Build a unique k-mer database from genome assemblies\n\nUsage: orion-kmer build [OPTIONS] --kmer-size <KMER_SIZE> --genomes <GENOME_FILES>... --output-file <OUTPUT_FILE>\n");
     else if (cmd == "compare")
@@ -365,6 +365,14 @@ static int run_count(const Args &a) {
     uint64_t min_count = 1;
     if (get_one(a, "min-count", ms) && !parse_u64(ms, min_count))
         return usage_error("invalid value '" + ms + "' for '--min-count <MIN_COUNT>'");
+    // --histogram <FILE>: the count histogram of the WHOLE table (--min-count
+    // does not apply), counts above --histogram-max lumped into its bin (an
+    // extension; jellyfish histo's default high bin)
+    std::string hist_path, hm;
+    const bool want_hist = get_one(a, "histogram", hist_path);
+    uint64_t hist_max = 10000;
+    if (get_one(a, "histogram-max", hm) && (!parse_u64(hm, hist_max) || hist_max == 0 || hist_max > (uint64_t(1) << 20)))
+        return usage_error("invalid value '" + hm + "' for '--histogram-max <HISTOGRAM_MAX>'");
     // --wide: opt-in two-u64 keys for k in 33..64 (not in the reference, whose
     // error for k > 32 is kept byte-identical without it)
     std::string wflag;
@@ -389,6 +397,15 @@ static int run_count(const Args &a) {
     // count.rs:106-137: filter, sort (the table already is) and write, streamed
     // off the GPU while the previous chunk is formatted
     phase("counted");
+    if (want_hist) {  // before the table is drained: read from the count's own runs, no gather
+        std::vector<uint64_t> hist(hist_max + 1);
+        if (okm_group_count_histogram(grp, hist.data(), hist.size(), nullptr) != OKM_OK)
+            return die("GPU engine failure while taking the count histogram: " + err_detail());
+        if (okm_write_histogram_tsv(hist_path.c_str(), hist.data(), hist.size()) != OKM_OK)
+            return die("Failed to get output writer for histogram file: " + dbg_path(hist_path));
+        info("orion_kmer::commands::count", "Successfully wrote the count histogram to " + dbg_path(hist_path));
+        phase("histogram");
+    }
     okm_status s = okm_group_write_counts_tsv(grp, out.c_str(), min_count, nullptr);
     phase("written");
     if (s != OKM_OK) return die("Failed to get output writer for counts file: " + dbg_path(out));
@@ -934,6 +951,8 @@ int main(int argc, char **argv) {
         spec.push_back({"min-count", 'm', true, false});
         spec.push_back({"wide", 0, false, false});
         spec.push_back({"gpus", 0, true, false});
+        spec.push_back({"histogram", 0, true, false});
+        spec.push_back({"histogram-max", 0, true, false});
     } else if (cmd == "build") {
         spec.push_back({"kmer-size", 'k', true, false});
         spec.push_back({"genomes", 'g', true, true});

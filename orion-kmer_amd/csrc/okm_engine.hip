@@ -3455,6 +3455,62 @@ okm_status okm_fetch_counts(okm_ctx *c, uint64_t min_count, uint64_t *keys, uint
     return fetch_result(c, min_count, keys, counts, cap, n, dst_on_device != 0);
 }
 
+// The count histogram of the table in the representation it lies in: the
+// pending per-item runs (only their counts are read; no gather, no run block
+// taken), a dense device table, or a host-resident one, whose counts alone go
+// up in slices.  Nothing of the table changes hands.
+okm_status okm_count_histogram(okm_ctx *c, uint64_t *hist, uint64_t n_bins, okm_count_summary *summary) {
+    if (!c || !hist) return fail(OKM_E_ARG, "okm_count_histogram: null argument");
+    if (n_bins < 2 || n_bins > (uint64_t(1) << 20) + 1)
+        return fail(OKM_E_ARG, "okm_count_histogram: n_bins " + std::to_string(n_bins) + " is not in 2..=2^20+1");
+    if (c->mode == OKM_MODE_SET) return fail(OKM_E_STATE, "okm_count_histogram: a set-mode context has no counts");
+    HIP_TRY(hipSetDevice(c->device));
+    OKM_TRY(okm_count(c, nullptr));
+    memset(hist, 0, n_bins * sizeof(uint64_t));
+    if (summary) *summary = okm_count_summary{};
+    const uint64_t n = c->n_res;
+    if (n == 0) return OKM_OK;
+    unsigned long long *dh = nullptr;  // n_bins bins, then entries | sum of counts | max count
+    Blocks scratch(*c->pool);
+    OKM_TRY(scratch.get(n_bins + 3, &dh));
+    HIP_TRY(hipMemsetAsync(dh, 0, (n_bins + 3) * sizeof(unsigned long long), c->stream));
+    if (c->pend.on) {
+        c->timer.begin(c->stream);
+        launch_hist_items(c->stream, c->pend.items, c->pend.nitems, c->pend.n_out, c->pend.sc, c->pend.narrow, n_bins,
+                          dh, dh + n_bins);
+        c->timer.end(c->stream, "count_histogram", (c->pend.narrow ? 4.0 : 8.0) * (double)n);
+    } else if (!c->res_host) {
+        c->timer.begin(c->stream);
+        launch_hist_dense(c->stream, c->res_counts, n, n_bins, dh, dh + n_bins);
+        c->timer.end(c->stream, "count_histogram", 8.0 * (double)n);
+    } else {
+        uint64_t sl = uint64_t(1) << 26;
+        if (const int64_t e = test_knob(OKM_TEST_HIST_SLICE); e > 0) sl = (uint64_t)e;  // tests: several / ragged slices
+        sl = std::min(sl, n);
+        uint64_t *dc = nullptr;
+        OKM_TRY(scratch.get(sl, &dc));
+        for (uint64_t o = 0; o < n; o += sl) {  // one buffer: slice i + 1's copy queues behind slice i's kernel
+            const uint64_t len = std::min(sl, n - o);
+            HIP_TRY(hipMemcpyAsync(dc, c->res_counts + o, len * 8, hipMemcpyHostToDevice, c->stream));
+            c->timer.begin(c->stream);
+            launch_hist_dense(c->stream, dc, len, n_bins, dh, dh + n_bins);
+            c->timer.end(c->stream, "count_histogram", 8.0 * (double)len);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    unsigned long long sm[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(hist, dh, n_bins * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(sm, dh + n_bins, sizeof(sm), hipMemcpyDeviceToHost, c->stream));
+    OKM_TRY(sync(c));
+    scratch.free_all();
+    if (summary) {
+        summary->n_distinct = sm[0];
+        summary->n_instances = sm[1];
+        summary->max_count = sm[2];
+    }
+    return OKM_OK;
+}
+
 okm_status okm_finish_counts(okm_ctx *c, uint64_t min_count, uint64_t **keys, uint64_t **counts, uint64_t *n) {
     if (!c || !keys || !n) return fail(OKM_E_ARG, "null argument");
     *keys = nullptr;

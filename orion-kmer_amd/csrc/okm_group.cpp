@@ -290,6 +290,33 @@ okm_status okm_group_finish_counts(okm_group *g, uint64_t min_count, uint64_t **
     return OKM_OK;
 }
 
+// The owners hold disjoint key ranges: their histograms, entries and instances
+// add, and the largest count is the largest of theirs.
+okm_status okm_group_count_histogram(okm_group *g, uint64_t *hist, uint64_t n_bins, okm_count_summary *summary) {
+    if (!g || !hist) return okm::fail(OKM_E_ARG, "okm_group_count_histogram: null argument");
+    if (n_bins < 2 || n_bins > (uint64_t(1) << 20) + 1)
+        return okm::fail(OKM_E_ARG, "okm_group_count_histogram: n_bins " + std::to_string(n_bins) + " is not in 2..=2^20+1");
+    if ((g->mode & 0xff) == OKM_MODE_SET)
+        return okm::fail(OKM_E_STATE, "okm_group_count_histogram: a set-mode group has no counts");
+    okm_status s = okm_group_count(g, nullptr);
+    if (s != OKM_OK) return s;
+    okm_count_summary tot{};
+    std::vector<uint64_t> part(g->w.size() > 1 ? n_bins : 0);
+    memset(hist, 0, n_bins * sizeof(uint64_t));
+    for (size_t r = 0; r < g->w.size(); ++r) {
+        okm_count_summary sm{};
+        uint64_t *dst = r == 0 ? hist : part.data();
+        if ((s = okm_count_histogram(g->w[r].ctx, dst, n_bins, &sm)) != OKM_OK) return s;
+        if (r)
+            for (uint64_t b = 0; b < n_bins; ++b) hist[b] += part[b];
+        tot.n_distinct += sm.n_distinct;
+        tot.n_instances += sm.n_instances;
+        tot.max_count = std::max(tot.max_count, sm.max_count);
+    }
+    if (summary) *summary = tot;
+    return OKM_OK;
+}
+
 // count.rs:106-137 straight from the device: every owner's range (rank
 // order = the sorted global table) is copied off the GPU in chunks into two
 // page-locked buffers by a copy thread while the host threads filter, format

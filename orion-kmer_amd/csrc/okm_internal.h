@@ -314,6 +314,17 @@ void launch_filter_scatter(void *stream, const uint64_t *keys, const uint64_t *c
                            uint64_t *dst_keys, uint64_t *dst_counts, bool wide);
 uint32_t filter_blocks(uint64_t n);
 
+// Count histogram (okm_hist.hip): hist[min(count, n_bins - 1)] += 1 per entry;
+// summary[0] += entries, [1] += sum of counts, [2] = max count.  Both
+// accumulate into what hist / summary hold (zeroed by the caller).  The items
+// form reads the pending segmented table's counts (u32 when narrow) where the
+// count kernels staged them; the dense form a flat u64 array.
+void launch_hist_items(void *stream, const DevItem *items, uint32_t nitems, const unsigned long long *n_out,
+                       const uint64_t *counts, bool narrow, uint64_t n_bins, unsigned long long *hist,
+                       unsigned long long *summary);
+void launch_hist_dense(void *stream, const uint64_t *counts, uint64_t n, uint64_t n_bins, unsigned long long *hist,
+                       unsigned long long *summary);
+
 // |A ∩ B| of sorted unique arrays (merge-path style binary search per element).
 void launch_intersect_count(void *stream, const uint64_t *a, uint64_t na, const uint64_t *b,
                             uint64_t nb, unsigned long long *out, bool wide);

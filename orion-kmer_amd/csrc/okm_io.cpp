@@ -1077,6 +1077,21 @@ okm_status okm_write_counts_tsv(const char *path, uint8_t k, const uint64_t *key
                                    nullptr);
 }
 
+// jellyfish histo's lines without its zero bins: "COUNT\tKMERS\n", ascending;
+// the last bin stands for every count >= n_bins - 1 and carries that label.
+okm_status okm_write_histogram_tsv(const char *path, const uint64_t *hist, uint64_t n_bins) {
+    if (!path || (!hist && n_bins)) return fail(OKM_E_ARG, "okm_write_histogram_tsv: null argument");
+    std::string out;
+    for (uint64_t b = 0; b < n_bins; ++b)
+        if (hist[b]) {
+            out += std::to_string(b);
+            out += '\t';
+            out += std::to_string(hist[b]);
+            out += '\n';
+        }
+    return okm_write_file(path, reinterpret_cast<const uint8_t *>(out.data()), out.size());
+}
+
 okm_status okm_write_file(const char *path, const uint8_t *data, uint64_t n) {
     if (!path) return fail(OKM_E_ARG, "null path");
     OutWriter w;

@@ -24,7 +24,7 @@ from ._lib import (OKM_E_DEVICE, OKM_E_INVALID_K, OKM_E_IO, OKM_E_PARSE, OKM_E_R
 __all__ = [
     "seq_to_u64", "u64_to_seq", "reverse_complement_u64", "canonical_u64",
     "KmerCounter", "DeviceBuffer", "device_count", "device_arch", "pack_records",
-    "parse_fastx", "read_fastx_file", "write_counts_tsv", "synth_reads", "synth_reads_device", "synth_long_reads",
+    "parse_fastx", "read_fastx_file", "write_counts_tsv", "write_histogram_tsv", "synth_reads", "synth_reads_device", "synth_long_reads",
     "run_count", "run_build", "run_compare", "KmerDb", "OkmError",
     "KmerSet", "Classifier", "run_query", "run_classify", "read_fastx_records",
     "Comm", "comm_unique_id", "owner_bounds", "synth_reads_device", "distributed_compare",
@@ -230,6 +230,12 @@ def write_counts_tsv(path: str, k: int, keys: np.ndarray, counts: np.ndarray) ->
           "okm_write_counts_tsv")
 
 
+def write_histogram_tsv(path: str, hist: np.ndarray) -> None:
+    """COUNT<TAB>KMERS lines of a count_histogram result (zero bins omitted)."""
+    hist = np.ascontiguousarray(hist, dtype=np.uint64)
+    check(lib().okm_write_histogram_tsv(path.encode(), hist.ctypes.data, len(hist)), "okm_write_histogram_tsv")
+
+
 def synth_reads(n_reads: int, read_len: int = 150, genome_len: int = 100_000_000, genome_seed: int = 2,
                 seed: int = 2, first_read: int = 0, sub_rate: float = 0.001, n_rate: float = 0.0001,
                 threads: int = 0) -> np.ndarray:
@@ -378,6 +384,16 @@ class KmerCounter:
         check(lib().okm_fetch_counts(self.ctx, min_count, keys.ctypes.data, counts.ctypes.data, n.value,
                                      byref(got), 0), "okm_fetch_counts")
         return keys[:got.value], counts[:got.value]
+
+    def count_histogram(self, n_bins: int = 10001) -> Tuple[np.ndarray, Dict[str, int]]:
+        """hist[c] = distinct keys counted exactly c times (the last bin: >=
+        n_bins - 1), and {n_distinct, n_instances, max_count}; read from the
+        table where it lies (okm_count_histogram)."""
+        hist = np.zeros(max(int(n_bins), 0), dtype=np.uint64)
+        sm = _lib.CountSummary()
+        check(lib().okm_count_histogram(self.ctx, hist.ctypes.data, int(n_bins) & (2 ** 64 - 1), byref(sm)),
+              "okm_count_histogram")
+        return hist, {f: int(getattr(sm, f)) for f, _ in _lib.CountSummary._fields_}
 
     def result_device(self) -> Tuple[int, int, int]:
         k = c_void_p()

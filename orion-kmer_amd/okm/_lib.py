@@ -66,6 +66,11 @@ class EngineInfo(Structure):
                 ("spills", c_uint32), ("l1_blocks", c_uint32)]
 
 
+class CountSummary(Structure):
+    """okm_count_summary."""
+    _fields_ = [("n_distinct", c_uint64), ("n_instances", c_uint64), ("max_count", c_uint64)]
+
+
 class Key128(Structure):
     """okm_key128: value = hi * 2**64 + lo."""
     _fields_ = [("lo", c_uint64), ("hi", c_uint64)]
@@ -170,6 +175,9 @@ PROTOTYPES = {
     "okm_group_owner": (c_void_p, [c_void_p, c_int]),
     "okm_group_finish_counts": (c_int, [c_void_p, c_uint64, _PP64, _PP64, _P64]),
     "okm_group_write_counts_tsv": (c_int, [c_void_p, c_char_p, c_uint64, _P64]),
+    "okm_count_histogram": (c_int, [c_void_p, c_void_p, c_uint64, POINTER(CountSummary)]),
+    "okm_group_count_histogram": (c_int, [c_void_p, c_void_p, c_uint64, POINTER(CountSummary)]),
+    "okm_write_histogram_tsv": (c_int, [c_char_p, c_void_p, c_uint64]),
     "okm_synth_reads_device": (c_int, [c_uint64, c_uint64, c_uint64, c_uint64, c_uint64, c_uint32, c_double,
                                        c_double, c_void_p, c_int]),
     "okm_test_set": (None, [c_int, c_int64]),

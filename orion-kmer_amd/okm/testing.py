@@ -30,6 +30,7 @@ KNOBS: Dict[str, int] = {
     "group_over": 16,
     "l1_max_blocks": 17,
     "fail_alloc": 18,
+    "hist_slice": 19,
 }
 
 

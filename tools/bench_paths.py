@@ -27,6 +27,10 @@ input, warmup then timed steps bracketed by device syncs).
   --workload classify classify.rs:215-308 — probe a 32-reference database
                      (the genome split in 32 slices, ~100 M keys) against the
                      counted table of the batch (okm_classifier_probe_db).
+  --workload histogram okm_count_histogram on the counted configs[1] table as
+                     the count leaves it (per-item runs), and in the same
+                     process the gather a reader paid before it
+                     (compact_items): both kernels' HIP-event times.
 
 The CPU baseline is the C restatement (oracle/) on a bounded sample, 1 thread.
 """
@@ -150,6 +154,53 @@ def wl_build(args):
             "data": "synthetic (BASELINE configs[1] reads, device-resident)",
             "config": {"workload": "build: set of canonical 31-mers of 3,355,443 x 150 bp reads", "k": k,
                        "distinct": int(n)}}
+
+
+def wl_histogram(args):
+    """okm_count_histogram on the C2 table as the count leaves it (per-item
+    runs, u32 counts), then -- same process, same table -- the gather a reader
+    had to pay before it (compact_items, through result_device()).  Both times
+    are HIP-event times from kernel_stats()."""
+    k = 31
+    batch = c2_batch()
+    dbuf = okm.DeviceBuffer(len(batch))
+    dbuf.upload(batch)
+    n_bins = 10001
+    with okm.KmerCounter(k) as c:
+        c.add_device_batch(dbuf.address, len(batch))
+        distinct = c.count()
+        for _ in range(args.warmup):
+            c.count_histogram(n_bins)
+        c.set_timing(True)  # (clears the statistics: the count's own kernels stay out)
+        t = time.perf_counter()
+        for _ in range(args.steps):
+            hist, summary = c.count_histogram(n_bins)
+        wall = (time.perf_counter() - t) / args.steps
+        stats = c.kernel_stats()
+        assert "compact_items" not in stats, "the histogram gathered the pending table"
+        c.result_device()
+        stats = c.kernel_stats()
+        h, g = stats["count_histogram"], stats["compact_items"]
+        assert h["launches"] == args.steps and g["launches"] == 1
+        assert int(hist.sum()) == distinct == summary["n_distinct"]
+        h_ms, g_ms = h["total_ms"] / h["launches"], g["total_ms"]
+        alg = 4 * distinct  # the u32 staged counts, read once
+        assert h["alg_bytes"] == float(alg) * args.steps
+    dbuf.free()
+    return {"metric": "count histogram of the pending C2 table (k=31) on one MI355X, HIP-event ms", "value": round(h_ms, 4),
+            "unit": "ms", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "higher_is_better": False,
+            "dtype": "u32 counts",
+            "data": "synthetic (BASELINE configs[1] reads, device-resident)",
+            "config": {"workload": "histogram: 3,355,443 x 150 bp reads counted, spectrum read from the per-item runs",
+                       "k": k, "n_bins": n_bins, "distinct": int(distinct), "summary": summary,
+                       "hist_first_16": [int(x) for x in hist[:16]], "wall_ms_per_call": round(wall * 1e3, 3),
+                       "lib": os.path.basename(os.path.dirname(os.environ.get("OKM_LIB", ""))) or "build"},
+            "kernels": {"count_histogram_ms": round(h_ms, 4), "compact_items_ms": round(g_ms, 4),
+                        "histogram_over_gather": round(h_ms / g_ms, 4),
+                        "compact_items_alg_bytes": g["alg_bytes"]},
+            "roofline": {"bound": "hbm", "kernel": "k_hist_items<narrow>", "alg_bytes_per_step": alg,
+                         "achieved": round(alg / (h_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": round(alg / (h_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}}
 
 
 def ont_batch(gbases: float, seed: int = 4):
@@ -665,7 +716,8 @@ def wl_classify(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3"], required=True)
+    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram"],
+                    required=True)
     ap.add_argument("--no-ref", action="store_true", help="c3: skip the one-GPU reference table")
     ap.add_argument("--c3-reads", type=int, default=C3_READS,
                     help="c3: total reads (BASELINE configs[2]: 167,772,160; P local tables of the full size do not "
@@ -687,7 +739,7 @@ def main():
             testing.set_knob(name, int(val))
     c5 = wl_c5_dist if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.loopback else wl_c5
     out = {"query": wl_query, "build": wl_build, "wide": wl_wide, "classify": wl_classify,
-           "c5": c5, "c3": wl_c3_loop}[args.workload](args)
+           "c5": c5, "c3": wl_c3_loop, "histogram": wl_histogram}[args.workload](args)
     if out is not None:
         print(json.dumps(out), flush=True)
 
