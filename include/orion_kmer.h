@@ -184,6 +184,20 @@ typedef struct okm_count_summary {
 okm_status okm_count_histogram(okm_ctx *ctx, uint64_t *hist, uint64_t n_bins,
                                okm_count_summary *summary /* may be NULL */);
 
+/* counts[i] = the count of keys[i] in the counted table, 0 when it is absent
+ * -- what jellyfish `query` reports; an extension, the reference has none.
+ * keys: n canonical keys in any order, duplicates allowed (okm_key128 pairs in
+ * a k > 32 context), taken as given: a non-canonical key is simply absent
+ * (canonicalise with okm_canonical_u64 / okm_canonical_u128).  on_device != 0:
+ * keys and counts are device pointers on the context's device.  *n_found
+ * (optional) = queries that were present.  Counts first if batches are pending
+ * (as okm_result_size).  Read-only, like okm_count_histogram: the table stays
+ * where and as it lies (a count's per-item runs are searched in place, a
+ * host-resident table goes up in slices).  n == 0: OK, nothing touched.  A
+ * set-mode context has no counts: OKM_E_STATE. */
+okm_status okm_lookup_counts(okm_ctx *ctx, const uint64_t *keys, uint64_t n,
+                             uint64_t *counts, int on_device, uint64_t *n_found);
+
 /* Device pointers to the counted, sorted, unfiltered table (valid until the
  * next add/reset/destroy). */
 okm_status okm_result_device(okm_ctx *ctx, const uint64_t **d_keys, const uint64_t **d_counts,
@@ -370,6 +384,10 @@ okm_status okm_group_write_counts_tsv(okm_group *g, const char *path, uint64_t m
  * key ranges, so the histograms, n_distinct and n_instances add and max_count
  * is the largest. */
 okm_status okm_group_count_histogram(okm_group *g, uint64_t *hist, uint64_t n_bins, okm_count_summary *summary);
+/* okm_lookup_counts over the group (host buffers; counts first): the owners
+ * hold disjoint key ranges, so each query is found on at most one owner. */
+okm_status okm_group_lookup_counts(okm_group *g, const uint64_t *keys, uint64_t n,
+                                   uint64_t *counts, uint64_t *n_found);
 
 /* ------------------------------------------------------------------------
  * Instrumentation (bench.py measures kernels with HIP events on the

@@ -73,8 +73,8 @@ typedef enum okm_test_knob {
      * bookkeeping, one allocation at a time.  A clean run under a huge n
      * tells how many allocations it made. */
     OKM_TEST_FAIL_ALLOC = 18,
-    /* okm_count_histogram over a host-resident table: entries per uploaded
-     * slice of its counts instead of 2^26 */
+    /* in-place readers of a host-resident table (okm_count_histogram,
+     * okm_lookup_counts): entries per uploaded slice instead of 2^26 */
     OKM_TEST_HIST_SLICE = 19,
     OKM_TEST_KNOBS = 20
 } okm_test_knob;

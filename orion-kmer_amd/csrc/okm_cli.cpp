@@ -219,7 +219,7 @@ static const char *kVersion = "orion-kmer 0.1.0";
 
 static void print_help(const std::string &cmd) {
     if (cmd == "count")
-        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
+        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
     else if (cmd == "build")
         printf("Build a unique k-mer database from genome assemblies\n\nUsage: orion-kmer build [OPTIONS] --kmer-size <KMER_SIZE> --genomes <GENOME_FILES>... --output-file <OUTPUT_FILE>\n");
     else if (cmd == "compare")
@@ -353,6 +353,50 @@ static int feed_file_group(AsyncGroup &ag, const std::string &path, const char *
     return 0;
 }
 
+// The k-mers of a --lookup file: one k-mer of exactly k bases (A/C/G/T, either
+// case) per line, a trailing CR trimmed, blank lines and '>' lines skipped (a
+// FASTA of k-mers works).  text: the k-mers as written; keys: their canonical
+// keys, one u64 each, or lo | hi pairs for k > 32.
+struct LookupList {
+    std::vector<std::string> text;
+    std::vector<uint64_t> keys;
+};
+
+static int read_lookup_file(const std::string &path, uint8_t k, LookupList &out) {
+    uint8_t *data = nullptr;
+    uint64_t n = 0;
+    if (okm_read_file(path.c_str(), 1, &data, &n) != OKM_OK)
+        return die("Failed to get input reader for lookup file: " + dbg_path(path));
+    int rc = 0;
+    uint64_t line = 0;
+    for (uint64_t at = 0; at < n && !rc;) {
+        const uint8_t *nl = static_cast<const uint8_t *>(memchr(data + at, '\n', n - at));
+        const uint64_t end = nl ? (uint64_t)(nl - data) : n;
+        uint64_t len = end - at;
+        ++line;
+        if (len && data[at + len - 1] == '\r') --len;
+        if (len && data[at] != '>') {
+            okm_key128 w{};
+            uint64_t v = 0;
+            const bool ok = k > 32 ? okm_seq_to_u128(data + at, len, k, &w) : okm_seq_to_u64(data + at, len, k, &v);
+            if (!ok) {
+                rc = die("Invalid k-mer in lookup file " + dbg_path(path) + " at line " + std::to_string(line) +
+                         ": expected " + std::to_string(k) + " bases of A/C/G/T");
+            } else if (k > 32) {
+                w = okm_canonical_u128(w, k);
+                out.keys.push_back(w.lo);
+                out.keys.push_back(w.hi);
+            } else {
+                out.keys.push_back(okm_canonical_u64(v, k));
+            }
+            if (ok) out.text.emplace_back(reinterpret_cast<const char *>(data + at), len);
+        }
+        at = end + 1;
+    }
+    okm_free_result(data);
+    return rc;
+}
+
 // count.rs:40-141
 static int run_count(const Args &a) {
     uint8_t k;
@@ -373,12 +417,27 @@ static int run_count(const Args &a) {
     uint64_t hist_max = 10000;
     if (get_one(a, "histogram-max", hm) && (!parse_u64(hm, hist_max) || hist_max == 0 || hist_max > (uint64_t(1) << 20)))
         return usage_error("invalid value '" + hm + "' for '--histogram-max <HISTOGRAM_MAX>'");
+    // --lookup <FILE> --lookup-output <FILE>: the counts of the listed k-mers
+    // in the WHOLE table (--min-count does not apply), what jellyfish query
+    // prints (an extension); each flag needs the other
+    std::string look_path, look_out;
+    const bool want_look = get_one(a, "lookup", look_path);
+    if (want_look != get_one(a, "lookup-output", look_out))
+        return usage_error(std::string("the following required arguments were not provided:\n  ") +
+                           (want_look ? "--lookup-output <FILE>" : "--lookup <FILE>"));
     // --wide: opt-in two-u64 keys for k in 33..64 (not in the reference, whose
     // error for k > 32 is kept byte-identical without it)
     std::string wflag;
     const bool wide = get_one(a, "wide", wflag);
     if (k == 0 || k > (wide ? 64 : 32))
         return die("Invalid K-mer size: " + std::to_string(k) + ". Must be between 1 and " + (wide ? "64." : "32."));
+    // the lookup list is read and checked before the engine starts
+    LookupList look;
+    if (want_look) {
+        if ((rc = read_lookup_file(look_path, k, look))) return rc;
+        info("orion_kmer::commands::count",
+             "Read " + std::to_string(look.text.size()) + " k-mers to look up from " + dbg_path(look_path));
+    }
     // one table across all inputs (count.rs:48), on g_gpus GPUs (default 1),
     // started while the first input is parsed
     phase("start");
@@ -405,6 +464,22 @@ static int run_count(const Args &a) {
             return die("Failed to get output writer for histogram file: " + dbg_path(hist_path));
         info("orion_kmer::commands::count", "Successfully wrote the count histogram to " + dbg_path(hist_path));
         phase("histogram");
+    }
+    if (want_look) {  // searched in the count's own runs, as the histogram reads them
+        std::vector<uint64_t> cnt(look.text.size());
+        if (okm_group_lookup_counts(grp, look.keys.data(), cnt.size(), cnt.data(), nullptr) != OKM_OK)
+            return die("GPU engine failure while looking up k-mers: " + err_detail());
+        std::string lines;
+        for (size_t i = 0; i < cnt.size(); ++i) {
+            lines += look.text[i];
+            lines += '\t';
+            lines += std::to_string(cnt[i]);
+            lines += '\n';
+        }
+        if (okm_write_file(look_out.c_str(), reinterpret_cast<const uint8_t *>(lines.data()), lines.size()) != OKM_OK)
+            return die("Failed to get output writer for lookup output file: " + dbg_path(look_out));
+        info("orion_kmer::commands::count", "Successfully wrote the looked-up counts to " + dbg_path(look_out));
+        phase("lookup");
     }
     okm_status s = okm_group_write_counts_tsv(grp, out.c_str(), min_count, nullptr);
     phase("written");
@@ -953,6 +1028,8 @@ int main(int argc, char **argv) {
         spec.push_back({"gpus", 0, true, false});
         spec.push_back({"histogram", 0, true, false});
         spec.push_back({"histogram-max", 0, true, false});
+        spec.push_back({"lookup", 0, true, false});
+        spec.push_back({"lookup-output", 0, true, false});
     } else if (cmd == "build") {
         spec.push_back({"kmer-size", 'k', true, false});
         spec.push_back({"genomes", 'g', true, true});

@@ -3511,6 +3511,121 @@ okm_status okm_count_histogram(okm_ctx *c, uint64_t *hist, uint64_t n_bins, okm_
     return OKM_OK;
 }
 
+// The counts of given keys, searched in the representation the table lies in:
+// the pending per-item runs (a first-key index over the items, built in
+// scratch per call, then the item's run), a dense device table, or a
+// host-resident one, which goes up in slices of keys and counts, every slice
+// searched for all queries (a slice writes only the queries it finds).  Host
+// queries go through scratch in chunks of kLookupChunk, so the call's device
+// footprint does not grow with n.  Nothing of the table changes hands.
+constexpr uint64_t kLookupChunk = uint64_t(1) << 22;
+
+okm_status okm_lookup_counts(okm_ctx *c, const uint64_t *keys, uint64_t n, uint64_t *counts, int on_device,
+                             uint64_t *n_found) {
+    if (!c || (n && (!keys || !counts))) return fail(OKM_E_ARG, "okm_lookup_counts: null argument");
+    if (n >> 40) return fail(OKM_E_ARG, "okm_lookup_counts: more than 2^40 queries");
+    if (c->mode == OKM_MODE_SET) return fail(OKM_E_STATE, "okm_lookup_counts: a set-mode context has no counts");
+    if (n_found) *n_found = 0;
+    if (n == 0) return OKM_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    OKM_TRY(okm_count(c, nullptr));
+    const uint64_t nt = c->n_res, kw = c->kw;
+    if (nt == 0) {
+        if (!on_device) {
+            memset(counts, 0, n * sizeof(uint64_t));
+            return OKM_OK;
+        }
+        HIP_TRY(hipMemsetAsync(counts, 0, n * sizeof(uint64_t), c->stream));
+        return sync(c);
+    }
+    const bool pending = c->pend.on, sliced = !pending && c->res_host;
+    Blocks scratch(*c->pool);
+    unsigned long long *dfound = nullptr;
+    OKM_TRY(scratch.get(1, &dfound));
+    HIP_TRY(hipMemsetAsync(dfound, 0, sizeof(unsigned long long), c->stream));
+    // the table's side
+    unsigned long long *pos = nullptr, *stmp = nullptr;
+    uint64_t *first = nullptr, *tk = nullptr, *tc = nullptr;
+    LookItem *desc = nullptr;
+    uint64_t sl = nt;
+    if (pending) {
+        const uint32_t ni = c->pend.nitems;
+        OKM_TRY(scratch.get((size_t)ni + 1, &pos));
+        OKM_TRY(scratch.get(scan_tmp_elems((uint64_t)ni + 1), &stmp));
+        OKM_TRY(scratch.get((size_t)ni * kw, &first));
+        OKM_TRY(scratch.get((size_t)ni, &desc));
+    } else if (sliced) {
+        sl = uint64_t(1) << 26;
+        if (const int64_t e = test_knob(OKM_TEST_HIST_SLICE); e > 0) sl = (uint64_t)e;  // tests: several / ragged slices
+        sl = std::min(sl, nt);
+        OKM_TRY(scratch.get(sl * kw, &tk));
+        OKM_TRY(scratch.get(sl, &tc));
+    }
+    // the queries' side
+    const uint64_t chunk = on_device ? n : std::min(n, kLookupChunk);
+    uint64_t *dq = nullptr, *dc = nullptr;
+    std::vector<uint64_t> part;  // host queries of a sliced table: one chunk's hits in one slice
+    if (!on_device) {
+        OKM_TRY(scratch.get(chunk * kw, &dq));
+        OKM_TRY(scratch.get(chunk, &dc));
+        if (sliced) {
+            part.resize(chunk);
+            memset(counts, 0, n * sizeof(uint64_t));
+        }
+    } else if (sliced) {
+        HIP_TRY(hipMemsetAsync(counts, 0, n * sizeof(uint64_t), c->stream));
+    }
+    bool first_launch = true;
+    for (uint64_t o = 0; o < nt; o += sl) {  // one pass unless the table is host-resident
+        const uint64_t len = std::min(sl, nt - o);
+        if (sliced) {
+            HIP_TRY(hipMemcpyAsync(tk, c->res_keys + o * kw, len * kw * 8, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(tc, c->res_counts + o, len * 8, hipMemcpyHostToDevice, c->stream));
+        }
+        for (uint64_t qo = 0; qo < n; qo += chunk) {
+            const uint64_t nq = std::min(chunk, n - qo);
+            const uint64_t *q = keys + qo * kw;
+            uint64_t *out = counts + qo;
+            if (!on_device) {
+                HIP_TRY(hipMemcpyAsync(dq, q, nq * kw * 8, hipMemcpyHostToDevice, c->stream));
+                if (sliced) HIP_TRY(hipMemsetAsync(dc, 0, nq * 8, c->stream));
+                q = dq;
+                out = dc;
+            }
+            c->timer.begin(c->stream);
+            if (pending) {
+                if (first_launch)
+                    launch_lookup_index(c->stream, c->pend.items, c->pend.nitems, c->pend.n_out, c->pend.sk, c->wide, pos,
+                                        stmp, first, desc);
+                launch_lookup_items(c->stream, first, desc, pos + c->pend.nitems, c->pend.sc, c->pend.narrow, c->wide,
+                                    q, nq, out, dfound);
+            } else {
+                launch_lookup_dense(c->stream, sliced ? tk : c->res_keys, sliced ? tc : c->res_counts, len, c->wide, q,
+                                    nq, out, dfound, sliced);
+            }
+            // the queries in and the counts out, once per query however many slices search it
+            c->timer.end(c->stream, "lookup_counts", o == 0 ? (8.0 * kw + 8.0) * (double)nq : 0.0);
+            first_launch = false;
+            HIP_TRY(hipGetLastError());
+            if (on_device) continue;
+            if (!sliced) {
+                HIP_TRY(hipMemcpyAsync(counts + qo, dc, nq * 8, hipMemcpyDeviceToHost, c->stream));
+            } else {
+                HIP_TRY(hipMemcpyAsync(part.data(), dc, nq * 8, hipMemcpyDeviceToHost, c->stream));
+                OKM_TRY(sync(c));
+                for (uint64_t i = 0; i < nq; ++i)
+                    if (part[i]) counts[qo + i] = part[i];
+            }
+        }
+    }
+    unsigned long long found = 0;
+    HIP_TRY(hipMemcpyAsync(&found, dfound, sizeof(found), hipMemcpyDeviceToHost, c->stream));
+    OKM_TRY(sync(c));
+    scratch.free_all();
+    if (n_found) *n_found = found;
+    return OKM_OK;
+}
+
 okm_status okm_finish_counts(okm_ctx *c, uint64_t min_count, uint64_t **keys, uint64_t **counts, uint64_t *n) {
     if (!c || !keys || !n) return fail(OKM_E_ARG, "null argument");
     *keys = nullptr;

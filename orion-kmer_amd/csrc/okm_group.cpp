@@ -317,6 +317,31 @@ okm_status okm_group_count_histogram(okm_group *g, uint64_t *hist, uint64_t n_bi
     return OKM_OK;
 }
 
+// The owners hold disjoint key ranges: a query is found on one owner at most,
+// so the per-owner arrays (0 where absent) and n_found add.
+okm_status okm_group_lookup_counts(okm_group *g, const uint64_t *keys, uint64_t n, uint64_t *counts,
+                                   uint64_t *n_found) {
+    if (!g || (n && (!keys || !counts))) return okm::fail(OKM_E_ARG, "okm_group_lookup_counts: null argument");
+    if ((g->mode & 0xff) == OKM_MODE_SET)
+        return okm::fail(OKM_E_STATE, "okm_group_lookup_counts: a set-mode group has no counts");
+    if (n_found) *n_found = 0;
+    if (n == 0) return OKM_OK;
+    okm_status s = okm_group_count(g, nullptr);
+    if (s != OKM_OK) return s;
+    uint64_t tot = 0;
+    std::vector<uint64_t> part(g->w.size() > 1 ? n : 0);
+    for (size_t r = 0; r < g->w.size(); ++r) {
+        uint64_t found = 0;
+        uint64_t *dst = r == 0 ? counts : part.data();
+        if ((s = okm_lookup_counts(g->w[r].ctx, keys, n, dst, 0, &found)) != OKM_OK) return s;
+        if (r)
+            for (uint64_t i = 0; i < n; ++i) counts[i] += part[i];
+        tot += found;
+    }
+    if (n_found) *n_found = tot;
+    return OKM_OK;
+}
+
 // count.rs:106-137 straight from the device: every owner's range (rank
 // order = the sorted global table) is copied off the GPU in chunks into two
 // page-locked buffers by a copy thread while the host threads filter, format

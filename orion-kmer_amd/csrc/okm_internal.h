@@ -325,6 +325,31 @@ void launch_hist_items(void *stream, const DevItem *items, uint32_t nitems, cons
 void launch_hist_dense(void *stream, const uint64_t *counts, uint64_t n, uint64_t n_bins, unsigned long long *hist,
                        unsigned long long *summary);
 
+// Count lookup (okm_lookup.hip): out[i] = the count of query i in a sorted
+// table, *found += queries present.  wide: keys and queries are K128 (two u64
+// each; pointers stay uint64_t*, lengths count keys).
+// The pending segmented table is searched in two levels.  launch_lookup_index
+// builds the first: the first key of every item that owns one (not kItemEmpty,
+// n_out > 0), in item order, and a descriptor of its run.  Scratch: pos =
+// nitems + 1 words (pos[nitems] = items kept, read on the device), scan_tmp =
+// scan_tmp_elems(nitems + 1), first = nitems keys, desc = nitems LookItem.
+struct LookItem {
+    const uint64_t *keys;  // the run's ascending keys
+    uint64_t coff;         // its counts start at counts[coff] (u32 or u64 words)
+    uint64_t n;            // entries, > 0
+};
+void launch_lookup_index(void *stream, const DevItem *items, uint32_t nitems, const unsigned long long *n_out,
+                         const uint64_t *src_keys, bool wide, unsigned long long *pos, unsigned long long *scan_tmp,
+                         uint64_t *first, LookItem *desc);
+void launch_lookup_items(void *stream, const uint64_t *first, const LookItem *desc, const unsigned long long *n_desc,
+                         const uint64_t *src_counts, bool narrow, bool wide, const uint64_t *queries, uint64_t nq,
+                         uint64_t *out, unsigned long long *found);
+// A dense table keys[n] / counts[n].  hits_only: absent queries leave out[i]
+// as it is (one slice of a host-resident table; out zeroed by the caller).
+void launch_lookup_dense(void *stream, const uint64_t *keys, const uint64_t *counts, uint64_t n, bool wide,
+                         const uint64_t *queries, uint64_t nq, uint64_t *out, unsigned long long *found,
+                         bool hits_only);
+
 // |A ∩ B| of sorted unique arrays (merge-path style binary search per element).
 void launch_intersect_count(void *stream, const uint64_t *a, uint64_t na, const uint64_t *b,
                             uint64_t nb, unsigned long long *out, bool wide);

@@ -395,6 +395,27 @@ class KmerCounter:
               "okm_count_histogram")
         return hist, {f: int(getattr(sm, f)) for f, _ in _lib.CountSummary._fields_}
 
+    def lookup(self, keys: np.ndarray) -> np.ndarray:
+        """counts[i] = the count of canonical key i, 0 when it is absent; the
+        table is searched where it lies (okm_lookup_counts).  Wide contexts
+        take an (n, 2) [lo, hi] array or the same flattened to 2n."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        if self.wide and keys.size % 2:
+            raise ValueError("a wide context's keys are [lo, hi] pairs")
+        n = keys.size // 2 if self.wide else keys.size
+        counts = np.zeros(n, dtype=np.uint64)
+        check(lib().okm_lookup_counts(self.ctx, keys.ctypes.data, n, counts.ctypes.data, 0, None),
+              "okm_lookup_counts")
+        return counts
+
+    def lookup_device(self, d_keys: int, n: int, d_counts: int) -> int:
+        """lookup() with the n keys and the counts in device memory; returns
+        the number of queries that were present."""
+        found = c_uint64()
+        check(lib().okm_lookup_counts(self.ctx, c_void_p(d_keys), n, c_void_p(d_counts), 1, byref(found)),
+              "okm_lookup_counts(device)")
+        return found.value
+
     def result_device(self) -> Tuple[int, int, int]:
         k = c_void_p()
         c = c_void_p()

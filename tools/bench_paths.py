@@ -31,6 +31,12 @@ input, warmup then timed steps bracketed by device syncs).
                      the count leaves it (per-item runs), and in the same
                      process the gather a reader paid before it
                      (compact_items): both kernels' HIP-event times.
+  --workload lookup  okm_lookup_counts of 2^24 device queries (half present,
+                     half random) in the counted configs[1] table as the count
+                     leaves it, alternated in the same process with what a
+                     caller did before it: the gather (compact_items) plus
+                     torch.searchsorted and an index of the counts; then the
+                     same pair over the dense table, without the gather.
 
 The CPU baseline is the C restatement (oracle/) on a bounded sample, 1 thread.
 """
@@ -201,6 +207,143 @@ def wl_histogram(args):
             "roofline": {"bound": "hbm", "kernel": "k_hist_items<narrow>", "alg_bytes_per_step": alg,
                          "achieved": round(alg / (h_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(alg / (h_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}}
+
+
+class _DevView:
+    """__cuda_array_interface__ of engine-owned int64 device memory."""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<i8", "data": (ptr, False), "version": 3,
+                                         "strides": None}
+
+
+def wl_lookup(args):
+    """okm_lookup_counts against gather + torch.searchsorted on the C2 table.
+    Each repeat counts the batch again (the table is pending), times the
+    in-place lookup, then lets result_device() gather (compact_items, its
+    HIP-event time from kernel_stats()) and times torch.searchsorted + the
+    count index on the dense keys (torch events), then the lookup over the
+    dense table.  k = 31 keys are below 2^62, so an int64 view orders them as
+    the table does.  Every result array is asserted equal to torch's."""
+    import torch
+    k, nq = 31, 1 << 24
+    repeats = 3
+    steps = max(args.steps, 5)
+    batch = c2_batch()
+    dbuf = okm.DeviceBuffer(len(batch))
+    dbuf.upload(batch)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(24)
+    with okm.KmerCounter(k) as other:  # the present half: sampled from a second counter's table
+        other.add_device_batch(dbuf.address, len(batch))
+        hk, _ = other.result(1)
+        distinct = len(hk)
+        tk = torch.from_numpy(hk.view(np.int64)).cuda()
+        present = tk[torch.randint(0, distinct, (nq // 2,), device="cuda", generator=gen)]
+        del tk, hk
+    rand = torch.randint(0, 1 << 62, (nq - nq // 2,), device="cuda", generator=gen)
+    q = torch.cat([present, rand])[torch.randperm(nq, device="cuda", generator=gen)].contiguous()
+    del present, rand
+    out = torch.empty(nq, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+
+    def ev_ms(fn, n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(n):
+            r = fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / n, r
+
+    def lookup_ms(c):
+        """(HIP-event ms of the lookup's launches, wall ms) per call, and n_found."""
+        for _ in range(args.warmup):
+            c.lookup_device(q.data_ptr(), nq, out.data_ptr())
+        before = c.kernel_stats().get("lookup_counts", {"launches": 0, "total_ms": 0.0})
+        t = time.perf_counter()
+        for _ in range(steps):
+            found = c.lookup_device(q.data_ptr(), nq, out.data_ptr())
+        wall = (time.perf_counter() - t) / steps
+        st = c.kernel_stats()["lookup_counts"]
+        assert st["launches"] - before["launches"] == steps
+        return (st["total_ms"] - before["total_ms"]) / steps, wall * 1e3, found
+
+    rows = []
+    with okm.KmerCounter(k) as c:
+        for rep in range(repeats):
+            c.reset()
+            c.add_device_batch(dbuf.address, len(batch))
+            assert c.count() == distinct
+            c.set_timing(True)
+            gathers = c.kernel_stats().get("compact_items", {"launches": 0, "total_ms": 0.0})
+            pend_ms, pend_wall, found = lookup_ms(c)
+            assert c.kernel_stats().get("compact_items", gathers)["launches"] == gathers["launches"], \
+                "the lookup gathered the pending table"
+            got_pending = out.clone()
+            t = time.perf_counter()
+            pk, pc, n = c.result_device()  # the gather a caller paid before
+            gather_wall = (time.perf_counter() - t) * 1e3
+            g = c.kernel_stats()["compact_items"]
+            assert g["launches"] == gathers["launches"] + 1 and n == distinct
+            gather_ms = g["total_ms"] - gathers["total_ms"]
+            tk, tc = torch.as_tensor(_DevView(pk, n), device="cuda"), torch.as_tensor(_DevView(pc, n), device="cuda")
+
+            def torch_lookup():
+                at = torch.searchsorted(tk, q).clamp_(max=n - 1)
+                return torch.where(tk[at] == q, tc[at], 0)
+
+            ev_ms(torch_lookup, args.warmup or 1)
+            t = time.perf_counter()
+            torch_ms, ref = ev_ms(torch_lookup, steps)
+            torch_wall = (time.perf_counter() - t) * 1e3 / steps
+            assert torch.equal(got_pending, ref), "pending lookup != torch.searchsorted"
+            assert found == int((ref > 0).sum())
+            dense_ms, dense_wall, dfound = lookup_ms(c)
+            assert torch.equal(out, ref) and dfound == found, "dense lookup != torch.searchsorted"
+            assert c.kernel_stats()["compact_items"]["launches"] == g["launches"]
+            rows.append({"lookup_pending_ms": pend_ms, "lookup_pending_wall_ms": pend_wall,
+                         "compact_items_ms": gather_ms, "gather_wall_ms": gather_wall,
+                         "torch_searchsorted_index_ms": torch_ms, "torch_wall_ms": torch_wall,
+                         "lookup_dense_ms": dense_ms, "lookup_dense_wall_ms": dense_wall})
+            log(json.dumps(rows[-1]))
+            del tk, tc, ref, got_pending
+    dbuf.free()
+
+    def col(name):
+        v = sorted(r[name] for r in rows)
+        return {"median": round(v[len(v) // 2], 4), "min": round(v[0], 4), "max": round(v[-1], 4)}
+
+    base = sorted(r["compact_items_ms"] + r["torch_searchsorted_index_ms"] for r in rows)
+    pend = col("lookup_pending_ms")
+    alg = 16 * nq
+    return {"metric": "counts of 2^24 k-mers looked up in the pending C2 table (k=31) on one MI355X, HIP-event ms",
+            "value": pend["median"], "unit": "ms", "n_gpus": 1, "steps": steps, "warmup": args.warmup,
+            "higher_is_better": False, "dtype": "u64 keys, u32 staged counts",
+            "data": "synthetic (BASELINE configs[1] reads, device-resident)",
+            "config": {"workload": "lookup: 3,355,443 x 150 bp reads counted; 2^24 shuffled device queries, half "
+                                   "sampled from the table, half random 62-bit values", "k": k, "queries": nq,
+                       "found": int(found), "distinct": int(distinct), "repeats": repeats,
+                       "lib": os.path.basename(os.path.dirname(os.environ.get("OKM_LIB", ""))) or "build"},
+            "pending": {"lookup_ms": pend, "lookup_wall_ms": col("lookup_pending_wall_ms"),
+                        "baseline_ms": {"median": round(base[len(base) // 2], 4), "min": round(base[0], 4),
+                                        "max": round(base[-1], 4)},
+                        "baseline_parts": {"compact_items_ms": col("compact_items_ms"),
+                                           "torch_searchsorted_index_ms": col("torch_searchsorted_index_ms"),
+                                           "gather_wall_ms": col("gather_wall_ms"), "torch_wall_ms": col("torch_wall_ms")},
+                        "lookup_over_baseline": round(pend["median"] / base[len(base) // 2], 4),
+                        # the margin is the larger run-to-run spread of the two, nothing more
+                        "spread_ms": round(max(base[-1] - base[0], pend["max"] - pend["min"]), 4),
+                        "no_slower_than_baseline": pend["median"] <= base[len(base) // 2] +
+                        max(base[-1] - base[0], pend["max"] - pend["min"])},
+            "dense": {"lookup_ms": col("lookup_dense_ms"), "lookup_wall_ms": col("lookup_dense_wall_ms"),
+                      "torch_searchsorted_index_ms": col("torch_searchsorted_index_ms"),
+                      "lookup_over_torch": round(col("lookup_dense_ms")["median"] /
+                                                 col("torch_searchsorted_index_ms")["median"], 4)},
+            "repeats": rows,
+            "roofline": {"bound": "latency (dependent loads of a search)", "kernel": "k_lookup_items<ull, narrow>",
+                         "alg_bytes_per_step": alg, "achieved": round(alg / (pend["median"] * 1e-3) / 1e9, 1),
+                         "peak": HBM_PEAK_GBS, "unit": "GB/s"}}
 
 
 def ont_batch(gbases: float, seed: int = 4):
@@ -716,7 +859,7 @@ def wl_classify(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram"],
+    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup"],
                     required=True)
     ap.add_argument("--no-ref", action="store_true", help="c3: skip the one-GPU reference table")
     ap.add_argument("--c3-reads", type=int, default=C3_READS,
@@ -739,7 +882,7 @@ def main():
             testing.set_knob(name, int(val))
     c5 = wl_c5_dist if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.loopback else wl_c5
     out = {"query": wl_query, "build": wl_build, "wide": wl_wide, "classify": wl_classify,
-           "c5": c5, "c3": wl_c3_loop, "histogram": wl_histogram}[args.workload](args)
+           "c5": c5, "c3": wl_c3_loop, "histogram": wl_histogram, "lookup": wl_lookup}[args.workload](args)
     if out is not None:
         print(json.dumps(out), flush=True)
 
