@@ -198,6 +198,46 @@ okm_status okm_count_histogram(okm_ctx *ctx, uint64_t *hist, uint64_t n_bins,
 okm_status okm_lookup_counts(okm_ctx *ctx, const uint64_t *keys, uint64_t n,
                              uint64_t *counts, int on_device, uint64_t *n_found);
 
+/* Per-record k-mer depth: how deep the k-mers of each record lie in the
+ * counted table -- `jellyfish query -s reads.fa` reduced per record; an
+ * extension, the reference has none.
+ * min ranges over the PRESENT windows only (0 when there is none); the read's
+ * shallowest window is  present < windows ? 0 : min.  So rows taken over the
+ * same reads against tables of disjoint keys combine without knowing each
+ * other: present, solid and sum add, max is the larger, min the smaller
+ * non-zero one, windows is the same in all of them (okm_group_read_depths, and
+ * the slices of a host-resident table, combine this way). */
+typedef struct okm_read_depth {
+    uint64_t windows;  /* valid k-windows of the record: exactly those okm_add_batch would count */
+    uint64_t present;  /* of them: the canonical k-mer is in the table */
+    uint64_t solid;    /* of them: its count >= min_count */
+    uint64_t sum;      /* sum of the present windows' counts, modulo 2^64 */
+    uint64_t min;      /* smallest count among present windows; 0 when present == 0 */
+    uint64_t max;      /* largest; 0 when present == 0 */
+} okm_read_depth;
+
+/* out[r] = the depth of record r.  Records as okm_add_batch takes them
+ * (normalized = 0: needletail normalize(false) applied here, by the same
+ * code); a window is a record's own and holds A/C/G/T only (either case, U as
+ * T); every record gets a row, zeros when it is empty or shorter than k.
+ * Counts first if batches are pending (as okm_result_size).  Read-only, like
+ * okm_lookup_counts: the read bytes go straight to the rows in one kernel, no
+ * key array exists and the table stays where and as it lies (a count's
+ * per-item runs are searched in place, a host-resident table goes up in
+ * slices).  The records go up in chunks of whole records, so the device
+ * footprint does not grow with the input.  An empty table: windows as they
+ * are, zeros elsewhere.  n_records == 0: OK, nothing touched.  A set-mode
+ * context has no counts: OKM_E_STATE. */
+okm_status okm_read_depths(okm_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, uint64_t n_records,
+                           int normalized, uint64_t min_count, okm_read_depth *out /* host, n_records */);
+/* The same over a device batch in okm_add_batch_device's layout (n_bytes
+ * bytes, records joined by OKM_RECORD_SEPARATOR; one after the last record is
+ * optional; bytes at and beyond n_bytes are never looked at).  A record's
+ * index is the number of separators before it; records past n_records are
+ * dropped.  d_out: n_records rows in device memory. */
+okm_status okm_read_depths_device(okm_ctx *ctx, const uint8_t *d_seq, uint64_t n_bytes, uint64_t n_records,
+                                  uint64_t min_count, okm_read_depth *d_out /* device, n_records */);
+
 /* Device pointers to the counted, sorted, unfiltered table (valid until the
  * next add/reset/destroy). */
 okm_status okm_result_device(okm_ctx *ctx, const uint64_t **d_keys, const uint64_t **d_counts,
@@ -388,6 +428,11 @@ okm_status okm_group_count_histogram(okm_group *g, uint64_t *hist, uint64_t n_bi
  * hold disjoint key ranges, so each query is found on at most one owner. */
 okm_status okm_group_lookup_counts(okm_group *g, const uint64_t *keys, uint64_t n,
                                    uint64_t *counts, uint64_t *n_found);
+/* okm_read_depths over the group (host buffers; counts first): every owner
+ * takes the depths of all the reads against its own key range, and the rows
+ * are combined by okm_read_depth's rule. */
+okm_status okm_group_read_depths(okm_group *g, const uint8_t *seq, const uint64_t *offsets, uint64_t n_records,
+                                 int normalized, uint64_t min_count, okm_read_depth *out);
 
 /* ------------------------------------------------------------------------
  * Instrumentation (bench.py measures kernels with HIP events on the

@@ -74,9 +74,12 @@ typedef enum okm_test_knob {
      * tells how many allocations it made. */
     OKM_TEST_FAIL_ALLOC = 18,
     /* in-place readers of a host-resident table (okm_count_histogram,
-     * okm_lookup_counts): entries per uploaded slice instead of 2^26 */
+     * okm_lookup_counts, okm_read_depths): entries per uploaded slice instead of 2^26 */
     OKM_TEST_HIST_SLICE = 19,
-    OKM_TEST_KNOBS = 20
+    /* okm_read_depths: bytes of packed records per uploaded chunk instead of
+     * 32 MiB (a chunk holds whole records, at least one) */
+    OKM_TEST_DEPTH_CHUNK = 20,
+    OKM_TEST_KNOBS = 21
 } okm_test_knob;
 
 /* value < 0 unsets the knob (the product default). */

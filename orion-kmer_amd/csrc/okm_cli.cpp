@@ -219,7 +219,7 @@ static const char *kVersion = "orion-kmer 0.1.0";
 
 static void print_help(const std::string &cmd) {
     if (cmd == "count")
-        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
+        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n      --depth <FASTX>              Take the k-mer depth of every record of FASTX in the whole table (extension)\n      --depth-output <FILE>        Where --depth writes id<TAB>windows<TAB>present<TAB>solid<TAB>sum<TAB>min<TAB>max, in input order\n      --depth-min-count <N>        A window is solid when its k-mer's count is at least N [default: 2]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
     else if (cmd == "build")
         printf("Build a unique k-mer database from genome assemblies\n\nUsage: orion-kmer build [OPTIONS] --kmer-size <KMER_SIZE> --genomes <GENOME_FILES>... --output-file <OUTPUT_FILE>\n");
     else if (cmd == "compare")
@@ -397,6 +397,46 @@ static int read_lookup_file(const std::string &path, uint8_t k, LookupList &out)
     return rc;
 }
 
+// The reader of the --depth reads, closed on every way out of run_count.
+struct DepthReader {
+    okm_reader *r = nullptr;
+    ~DepthReader() {
+        if (r) okm_reader_close(r);
+    }
+};
+
+// --depth: every batch of the reader through okm_group_read_depths, one line
+// per record in input order: id, windows, present, solid, sum, min, max.
+static int write_depths(okm_group *grp, okm_reader *r, const std::string &path, const std::string &out_path,
+                        uint64_t min_count) {
+    std::string lines;
+    std::vector<okm_read_depth> rows;
+    for (;;) {
+        const uint8_t *seq, *ids;
+        const uint64_t *off, *ioff;
+        uint64_t n;
+        if (okm_reader_next(r, 128ull << 20, &seq, &off, &n) != OKM_OK)
+            return die("Error reading record from " + path);
+        if (n == 0) break;
+        okm_reader_ids(r, &ids, &ioff);
+        rows.resize(n);
+        if (okm_group_read_depths(grp, seq, off, n, 1, min_count, rows.data()) != OKM_OK)
+            return die("GPU engine failure while taking read depths: " + err_detail());
+        for (uint64_t i = 0; i < n; ++i) {
+            lines.append(reinterpret_cast<const char *>(ids + ioff[i]), ioff[i + 1] - ioff[i]);
+            const okm_read_depth &d = rows[i];
+            for (uint64_t v : {d.windows, d.present, d.solid, d.sum, d.min, d.max}) {
+                lines += '\t';
+                lines += std::to_string(v);
+            }
+            lines += '\n';
+        }
+    }
+    if (okm_write_file(out_path.c_str(), reinterpret_cast<const uint8_t *>(lines.data()), lines.size()) != OKM_OK)
+        return die("Failed to get output writer for depth output file: " + dbg_path(out_path));
+    return 0;
+}
+
 // count.rs:40-141
 static int run_count(const Args &a) {
     uint8_t k;
@@ -425,6 +465,17 @@ static int run_count(const Args &a) {
     if (want_look != get_one(a, "lookup-output", look_out))
         return usage_error(std::string("the following required arguments were not provided:\n  ") +
                            (want_look ? "--lookup-output <FILE>" : "--lookup <FILE>"));
+    // --depth <FASTX> --depth-output <FILE> [--depth-min-count <N>]: per record
+    // of FASTX, how deep its k-mers lie in the WHOLE table (jellyfish query -s
+    // reduced per record; an extension); each of the two flags needs the other
+    std::string depth_path, depth_out, dm;
+    const bool want_depth = get_one(a, "depth", depth_path);
+    if (want_depth != get_one(a, "depth-output", depth_out))
+        return usage_error(std::string("the following required arguments were not provided:\n  ") +
+                           (want_depth ? "--depth-output <FILE>" : "--depth <FASTX>"));
+    uint64_t depth_min = 2;
+    if (get_one(a, "depth-min-count", dm) && (!parse_u64(dm, depth_min) || depth_min == 0))
+        return usage_error("invalid value '" + dm + "' for '--depth-min-count <N>'");
     // --wide: opt-in two-u64 keys for k in 33..64 (not in the reference, whose
     // error for k > 32 is kept byte-identical without it)
     std::string wflag;
@@ -437,6 +488,15 @@ static int run_count(const Args &a) {
         if ((rc = read_lookup_file(look_path, k, look))) return rc;
         info("orion_kmer::commands::count",
              "Read " + std::to_string(look.text.size()) + " k-mers to look up from " + dbg_path(look_path));
+    }
+    // the depth reads are opened before the engine starts (count's reader:
+    // its normalisation and extension decompression, ids kept) and read in
+    // batches once the table is counted
+    DepthReader depth_reader;
+    if (want_depth) {
+        const okm_status ds = okm_reader_open2(&depth_reader.r, depth_path.c_str(), 1, OKM_READ_IDS);
+        if (ds == OKM_E_IO) return die("Failed to get input reader for depth file: " + dbg_path(depth_path));
+        if (ds != OKM_OK) return die("Failed to parse FASTA/Q content from depth file: " + dbg_path(depth_path));
     }
     // one table across all inputs (count.rs:48), on g_gpus GPUs (default 1),
     // started while the first input is parsed
@@ -480,6 +540,11 @@ static int run_count(const Args &a) {
             return die("Failed to get output writer for lookup output file: " + dbg_path(look_out));
         info("orion_kmer::commands::count", "Successfully wrote the looked-up counts to " + dbg_path(look_out));
         phase("lookup");
+    }
+    if (want_depth) {  // the reads go straight to their rows; the table stays as it lies
+        if ((rc = write_depths(grp, depth_reader.r, depth_path, depth_out, depth_min))) return rc;
+        info("orion_kmer::commands::count", "Successfully wrote the read depths to " + dbg_path(depth_out));
+        phase("depth");
     }
     okm_status s = okm_group_write_counts_tsv(grp, out.c_str(), min_count, nullptr);
     phase("written");
@@ -1030,6 +1095,9 @@ int main(int argc, char **argv) {
         spec.push_back({"histogram-max", 0, true, false});
         spec.push_back({"lookup", 0, true, false});
         spec.push_back({"lookup-output", 0, true, false});
+        spec.push_back({"depth", 0, true, false});
+        spec.push_back({"depth-output", 0, true, false});
+        spec.push_back({"depth-min-count", 0, true, false});
     } else if (cmd == "build") {
         spec.push_back({"kmer-size", 'k', true, false});
         spec.push_back({"genomes", 'g', true, true});

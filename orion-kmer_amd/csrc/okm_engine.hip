@@ -3213,6 +3213,27 @@ okm_status okm_reset(okm_ctx *c) {
 
 static bool is_ws(uint8_t ch) { return ch == ' ' || ch == '\t' || ch == '\r' || ch == '\n'; }
 
+// Records [r0, r1) in the device batch layout: whitespace-free records, a
+// separator after each (dst holds their bytes + one per record).  Returns the
+// bytes written.
+static uint64_t pack_records(uint8_t *dst, const uint8_t *seq, const uint64_t *offsets, uint64_t r0, uint64_t r1,
+                             int normalized) {
+    uint64_t o = 0;
+    for (uint64_t r = r0; r < r1; ++r) {
+        const uint8_t *s = seq + offsets[r];
+        const uint64_t len = offsets[r + 1] - offsets[r];
+        if (normalized) {
+            if (len) std::memcpy(dst + o, s, len);
+            o += len;
+        } else {
+            for (uint64_t i = 0; i < len; ++i)
+                if (!is_ws(s[i])) dst[o++] = s[i];
+        }
+        dst[o++] = OKM_RECORD_SEPARATOR;
+    }
+    return o;
+}
+
 okm_status okm_add_batch(okm_ctx *c, const uint8_t *seq, const uint64_t *offsets, uint64_t n_records,
                          int normalized) {
     if (!c) return fail(OKM_E_ARG, "null ctx");
@@ -3224,21 +3245,8 @@ okm_status okm_add_batch(okm_ctx *c, const uint8_t *seq, const uint64_t *offsets
     HIP_TRY(hipSetDevice(c->device));
     OKM_TRY(sync(c));  // pinned buffer reuse
     OKM_TRY(ensure_pinned(c, total + n_records + 16));
-    // device batch layout: whitespace-free records + separator
     uint8_t *dst = c->pinned;
-    uint64_t o = 0;
-    for (uint64_t r = 0; r < n_records; ++r) {
-        const uint8_t *s = seq + offsets[r];
-        const uint64_t len = offsets[r + 1] - offsets[r];
-        if (normalized) {
-            std::memcpy(dst + o, s, len);
-            o += len;
-        } else {
-            for (uint64_t i = 0; i < len; ++i)
-                if (!is_ws(s[i])) dst[o++] = s[i];
-        }
-        dst[o++] = OKM_RECORD_SEPARATOR;
-    }
+    const uint64_t o = pack_records(dst, seq, offsets, 0, n_records, normalized);
     OKM_TRY(ensure_staging(c, o));
     HIP_TRY(hipMemcpyAsync(c->staging, dst, o, hipMemcpyHostToDevice, c->stream));
     OKM_TRY(before_add(c));
@@ -3623,6 +3631,176 @@ okm_status okm_lookup_counts(okm_ctx *c, const uint64_t *keys, uint64_t n, uint6
     OKM_TRY(sync(c));
     scratch.free_all();
     if (n_found) *n_found = found;
+    return OKM_OK;
+}
+
+// Per-record depths of reads against the table in the representation it lies
+// in, as okm_lookup_counts searches it: the pending per-item runs behind a
+// first-key index built once per call, a dense device table, or a
+// host-resident one in slices.  One launch sequence per (slice, batch):
+//   [launch_lookup_index, the first time]  k_depth_sep_count  scan
+//   k_read_depths  [k_depth_fix, after the batch's last slice]
+// A device batch keeps its rows in the caller's array across the slices.  Host
+// records go up in chunks of whole records (kDepthChunk bytes, at least one
+// record) through scratch sized for the largest chunk; with several slices
+// every slice scans every chunk again and the chunk's rows are combined on the
+// host (depth_combine), so the table goes up once whatever the input's size.
+constexpr uint64_t kDepthChunk = uint64_t(32) << 20;
+
+namespace {
+struct DepthCall {
+    okm_ctx *c;
+    Blocks scratch;
+    bool pending, sliced;
+    uint64_t sl, nslices;
+    unsigned long long *pos = nullptr, *stmp = nullptr, *tiles = nullptr;
+    uint64_t *first = nullptr, *tk = nullptr, *tc = nullptr;
+    LookItem *desc = nullptr;
+    bool indexed = false;
+    explicit DepthCall(okm_ctx *ctx) : c(ctx), scratch(*ctx->pool) {
+        pending = c->pend.on;
+        sliced = !pending && c->res_host && c->n_res;
+        sl = c->n_res;
+        if (sliced) {
+            sl = uint64_t(1) << 26;
+            if (const int64_t e = test_knob(OKM_TEST_HIST_SLICE); e > 0) sl = (uint64_t)e;  // tests: several / ragged slices
+            sl = std::min(sl, c->n_res);
+        }
+        nslices = c->n_res ? (c->n_res + sl - 1) / sl : 1;  // an empty table: one scan, for the windows
+    }
+    // the table's side of the scratch, and the tile words of a batch of at most max_bytes
+    okm_status prepare(uint64_t max_bytes) {
+        const uint64_t kw = c->kw;
+        if (pending) {
+            const uint32_t ni = c->pend.nitems;
+            OKM_TRY(scratch.get((size_t)ni + 1, &pos));
+            OKM_TRY(scratch.get(scan_tmp_elems((uint64_t)ni + 1), &stmp));
+            OKM_TRY(scratch.get((size_t)ni * kw, &first));
+            OKM_TRY(scratch.get((size_t)ni, &desc));
+        } else if (sliced) {
+            OKM_TRY(scratch.get(sl * kw, &tk));
+            OKM_TRY(scratch.get(sl, &tc));
+        }
+        const uint64_t nt = depth_tiles(max_bytes);
+        OKM_TRY(scratch.get(2 * nt + scan_tmp_elems(nt) + 1, &tiles));
+        return OKM_OK;
+    }
+    okm_status upload_slice(uint64_t si) {
+        if (!sliced) return OKM_OK;
+        const uint64_t o = si * sl, len = std::min(sl, c->n_res - o), kw = c->kw;
+        HIP_TRY(hipMemcpyAsync(tk, c->res_keys + o * kw, len * kw * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(tc, c->res_counts + o, len * 8, hipMemcpyHostToDevice, c->stream));
+        return OKM_OK;
+    }
+    // slice si's scan of one device batch into rows (zeroed before its slice 0)
+    okm_status scan(uint64_t si, const uint8_t *d_seq, uint64_t nb, uint64_t nrec, uint64_t min_count,
+                    okm_read_depth *rows, bool fix) {
+        DepthTable t;
+        if (pending) {
+            t.items = true;
+            t.narrow = c->pend.narrow;
+            t.first = first;
+            t.desc = desc;
+            t.n_desc = pos + c->pend.nitems;
+            t.sc = c->pend.sc;
+        } else {
+            t.keys = sliced ? tk : c->res_keys;
+            t.counts = sliced ? tc : c->res_counts;
+            t.n = c->n_res ? std::min(sl, c->n_res - si * sl) : 0;
+        }
+        c->timer.begin(c->stream);
+        if (pending && !indexed)
+            launch_lookup_index(c->stream, c->pend.items, c->pend.nitems, c->pend.n_out, c->pend.sk, c->wide, pos, stmp,
+                                first, desc);
+        indexed = true;
+        launch_read_depths(c->stream, d_seq, nb, nrec, c->k, c->wide, t, min_count, si == 0, tiles, rows);
+        if (fix) launch_read_depths_fix(c->stream, rows, nrec);
+        // the read bytes in and the rows out, once per batch however many slices scan it
+        c->timer.end(c->stream, "read_depths", si == 0 ? (double)nb + 48.0 * (double)nrec : 0.0);
+        HIP_TRY(hipGetLastError());
+        return OKM_OK;
+    }
+};
+}  // namespace
+
+okm_status okm_read_depths_device(okm_ctx *c, const uint8_t *d_seq, uint64_t n_bytes, uint64_t n_records,
+                                  uint64_t min_count, okm_read_depth *d_out) {
+    if (!c || (n_records && (!d_out || (!d_seq && n_bytes))))
+        return fail(OKM_E_ARG, "okm_read_depths_device: null argument");
+    if (n_bytes >> 42 || n_records >> 40) return fail(OKM_E_ARG, "okm_read_depths_device: batch too large");
+    if (c->mode == OKM_MODE_SET) return fail(OKM_E_STATE, "okm_read_depths_device: a set-mode context has no counts");
+    if (n_records == 0) return OKM_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    OKM_TRY(okm_count(c, nullptr));
+    DepthCall d(c);
+    const uint8_t *src = d_seq;
+    if (n_bytes) {
+        OKM_TRY(d.prepare(n_bytes));
+        if ((reinterpret_cast<uintptr_t>(d_seq) & 15u) != 0) {  // the scan loads 16-B words
+            uint64_t *copy = nullptr;
+            OKM_TRY(d.scratch.get(n_bytes / 8 + 1, &copy));
+            HIP_TRY(hipMemcpyAsync(copy, d_seq, n_bytes, hipMemcpyDeviceToDevice, c->stream));
+            src = reinterpret_cast<const uint8_t *>(copy);
+        }
+    }
+    HIP_TRY(hipMemsetAsync(d_out, 0, n_records * sizeof(okm_read_depth), c->stream));
+    for (uint64_t si = 0; n_bytes && si < d.nslices; ++si) {
+        OKM_TRY(d.upload_slice(si));
+        OKM_TRY(d.scan(si, src, n_bytes, n_records, min_count, d_out, si + 1 == d.nslices));
+    }
+    OKM_TRY(sync(c));
+    d.scratch.free_all();
+    return OKM_OK;
+}
+
+okm_status okm_read_depths(okm_ctx *c, const uint8_t *seq, const uint64_t *offsets, uint64_t n_records, int normalized,
+                           uint64_t min_count, okm_read_depth *out) {
+    if (!c || (n_records && (!offsets || !out))) return fail(OKM_E_ARG, "okm_read_depths: null argument");
+    if (n_records >> 40) return fail(OKM_E_ARG, "okm_read_depths: more than 2^40 records");
+    if (c->mode == OKM_MODE_SET) return fail(OKM_E_STATE, "okm_read_depths: a set-mode context has no counts");
+    if (n_records == 0) return OKM_OK;
+    if (offsets[n_records] != offsets[0] && !seq) return fail(OKM_E_ARG, "okm_read_depths: null seq");
+    HIP_TRY(hipSetDevice(c->device));
+    OKM_TRY(okm_count(c, nullptr));
+    // chunks of whole records: [first record, one past the last)
+    uint64_t chunk = kDepthChunk;
+    if (const int64_t e = test_knob(OKM_TEST_DEPTH_CHUNK); e > 0) chunk = (uint64_t)e;
+    std::vector<std::pair<uint64_t, uint64_t>> chunks;
+    uint64_t max_bytes = 0, max_recs = 0;
+    for (uint64_t r0 = 0; r0 < n_records;) {
+        uint64_t r1 = r0 + 1;  // at least one record, whatever its size
+        const auto bytes = [&](uint64_t e) { return offsets[e] - offsets[r0] + (e - r0); };
+        while (r1 < n_records && bytes(r1 + 1) <= chunk) ++r1;
+        if (bytes(r1) >> 42) return fail(OKM_E_ARG, "okm_read_depths: record too large");
+        chunks.emplace_back(r0, r1);
+        max_bytes = std::max(max_bytes, bytes(r1));
+        max_recs = std::max(max_recs, r1 - r0);
+        r0 = r1;
+    }
+    DepthCall d(c);
+    OKM_TRY(d.prepare(max_bytes));
+    uint64_t *dseq = nullptr;
+    okm_read_depth *drows = nullptr;
+    OKM_TRY(d.scratch.get(max_bytes / 8 + 1, &dseq));
+    OKM_TRY(d.scratch.get(max_recs, &drows));
+    std::vector<uint8_t> packed(max_bytes);
+    std::vector<okm_read_depth> part(d.nslices > 1 ? max_recs : 0);
+    for (uint64_t si = 0; si < d.nslices; ++si) {
+        OKM_TRY(d.upload_slice(si));
+        for (const auto &ch : chunks) {
+            const uint64_t r0 = ch.first, nr = ch.second - ch.first;
+            const uint64_t nb = pack_records(packed.data(), seq, offsets, r0, ch.second, normalized);
+            HIP_TRY(hipMemcpyAsync(dseq, packed.data(), nb, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemsetAsync(drows, 0, nr * sizeof(okm_read_depth), c->stream));
+            OKM_TRY(d.scan(si, reinterpret_cast<const uint8_t *>(dseq), nb, nr, min_count, drows, true));
+            okm_read_depth *dst = si == 0 ? out + r0 : part.data();
+            HIP_TRY(hipMemcpyAsync(dst, drows, nr * sizeof(okm_read_depth), hipMemcpyDeviceToHost, c->stream));
+            OKM_TRY(sync(c));  // `packed` and `part` are reused
+            if (si)
+                for (uint64_t i = 0; i < nr; ++i) depth_combine(out[r0 + i], part[i]);
+        }
+    }
+    d.scratch.free_all();
     return OKM_OK;
 }
 

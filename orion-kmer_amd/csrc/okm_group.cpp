@@ -342,6 +342,26 @@ okm_status okm_group_lookup_counts(okm_group *g, const uint64_t *keys, uint64_t 
     return OKM_OK;
 }
 
+// Every owner scans all the reads against its own key range; the rows combine
+// by okm_read_depth's rule (windows is the same on every owner: rank 0's).
+okm_status okm_group_read_depths(okm_group *g, const uint8_t *seq, const uint64_t *offsets, uint64_t n_records,
+                                 int normalized, uint64_t min_count, okm_read_depth *out) {
+    if (!g || (n_records && (!offsets || !out))) return okm::fail(OKM_E_ARG, "okm_group_read_depths: null argument");
+    if ((g->mode & 0xff) == OKM_MODE_SET)
+        return okm::fail(OKM_E_STATE, "okm_group_read_depths: a set-mode group has no counts");
+    if (n_records == 0) return OKM_OK;
+    okm_status s = okm_group_count(g, nullptr);
+    if (s != OKM_OK) return s;
+    std::vector<okm_read_depth> part(g->w.size() > 1 ? n_records : 0);
+    for (size_t r = 0; r < g->w.size(); ++r) {
+        okm_read_depth *dst = r == 0 ? out : part.data();
+        if ((s = okm_read_depths(g->w[r].ctx, seq, offsets, n_records, normalized, min_count, dst)) != OKM_OK) return s;
+        if (r)
+            for (uint64_t i = 0; i < n_records; ++i) okm::depth_combine(out[i], part[i]);
+    }
+    return OKM_OK;
+}
+
 // count.rs:106-137 straight from the device: every owner's range (rank
 // order = the sorted global table) is copied off the GPU in chunks into two
 // page-locked buffers by a copy thread while the host threads filter, format

@@ -350,6 +350,43 @@ void launch_lookup_dense(void *stream, const uint64_t *keys, const uint64_t *cou
                          const uint64_t *queries, uint64_t nq, uint64_t *out, unsigned long long *found,
                          bool hits_only);
 
+// Per-record k-mer depth (okm_depth.hip): one scan of a device batch (records
+// joined by separators, 16-byte aligned, n bytes) against one representation
+// of the table; rows[r] accumulates record r's okm_read_depth (r = separators
+// before the window, rows past nrec dropped).  The table is either dense
+// (keys / counts / n; n == 0: empty) or the pending runs behind
+// launch_lookup_index's index (items: first / desc / n_desc / sc / narrow).
+// Rows start zeroed; any number of launches (slices of a host-resident table)
+// add into them, exactly one of them with count_windows; the min field holds
+// the largest ~count until launch_read_depths_fix turns it round, once, after
+// the last launch.  tiles: 2 * depth_tiles(n) + scan_tmp_elems(depth_tiles(n))
+// words of scratch; depth_tiles(n) < 2^31.
+struct DepthTable {
+    const uint64_t *keys = nullptr, *counts = nullptr;
+    uint64_t n = 0;
+    bool items = false, narrow = false;
+    const uint64_t *first = nullptr;
+    const LookItem *desc = nullptr;
+    const unsigned long long *n_desc = nullptr;
+    const uint64_t *sc = nullptr;
+};
+uint64_t depth_tiles(uint64_t n_bytes);
+void launch_read_depths(void *stream, const uint8_t *seq, uint64_t n, uint64_t nrec, uint32_t k, bool wide,
+                        const DepthTable &t, uint64_t min_count, bool count_windows, unsigned long long *tiles,
+                        okm_read_depth *rows);
+void launch_read_depths_fix(void *stream, okm_read_depth *rows, uint64_t nrec);
+// a += b for rows taken over the same reads against tables of disjoint keys
+// (the slices of a host-resident table, the owners of a group): the rule
+// orion_kmer.h states for okm_read_depth.  windows is left as a's.
+inline void depth_combine(okm_read_depth &a, const okm_read_depth &b) {
+    if (!b.present) return;
+    a.min = a.present && a.min < b.min ? a.min : b.min;
+    a.max = a.max > b.max ? a.max : b.max;
+    a.present += b.present;
+    a.solid += b.solid;
+    a.sum += b.sum;
+}
+
 // |A ∩ B| of sorted unique arrays (merge-path style binary search per element).
 void launch_intersect_count(void *stream, const uint64_t *a, uint64_t na, const uint64_t *b,
                             uint64_t nb, unsigned long long *out, bool wide);

@@ -161,6 +161,10 @@ class DeviceBuffer:
 # record batches
 # ---------------------------------------------------------------------------
 
+# okm_read_depth (include/orion_kmer.h): six u64 per record
+READ_DEPTH_DTYPE = np.dtype([(f, "<u8") for f in ("windows", "present", "solid", "sum", "min", "max")])
+
+
 def pack_records(seqs: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
     """(bytes, offsets[n+1]) for okm_add_batch."""
     offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
@@ -415,6 +419,24 @@ class KmerCounter:
         check(lib().okm_lookup_counts(self.ctx, c_void_p(d_keys), n, c_void_p(d_counts), 1, byref(found)),
               "okm_lookup_counts(device)")
         return found.value
+
+    def read_depths(self, seqs: Sequence[bytes], min_count: int = 2, normalized: bool = False) -> np.ndarray:
+        """One row per record (READ_DEPTH_DTYPE: windows, present, solid, sum,
+        min, max): how deep the record's k-mers lie in the counted table,
+        which is searched where it lies (okm_read_depths).  min ranges over
+        the present windows; the record's shallowest window is
+        present < windows ? 0 : min."""
+        data, offs = pack_records(list(seqs))
+        out = np.zeros(len(offs) - 1, dtype=READ_DEPTH_DTYPE)
+        check(lib().okm_read_depths(self.ctx, data.ctypes.data, offs.ctypes.data, len(out), 1 if normalized else 0,
+                                    min_count, out.ctypes.data), "okm_read_depths")
+        return out
+
+    def read_depths_device(self, d_seq: int, nbytes: int, n_records: int, d_out: int, min_count: int = 2) -> None:
+        """read_depths() over a device batch (add_device_batch's layout) into
+        n_records rows of 48 bytes in device memory."""
+        check(lib().okm_read_depths_device(self.ctx, c_void_p(d_seq), nbytes, n_records, min_count, c_void_p(d_out)),
+              "okm_read_depths_device")
 
     def result_device(self) -> Tuple[int, int, int]:
         k = c_void_p()

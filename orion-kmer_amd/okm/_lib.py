@@ -180,6 +180,9 @@ PROTOTYPES = {
     "okm_write_histogram_tsv": (c_int, [c_char_p, c_void_p, c_uint64]),
     "okm_lookup_counts": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_int, _P64]),
     "okm_group_lookup_counts": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, _P64]),
+    "okm_read_depths": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_uint64, c_void_p]),
+    "okm_read_depths_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_uint64, c_void_p]),
+    "okm_group_read_depths": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_uint64, c_void_p]),
     "okm_synth_reads_device": (c_int, [c_uint64, c_uint64, c_uint64, c_uint64, c_uint64, c_uint32, c_double,
                                        c_double, c_void_p, c_int]),
     "okm_test_set": (None, [c_int, c_int64]),

@@ -32,15 +32,25 @@ KNOBS: Dict[str, int] = {
     "fail_alloc": 18,
     "hist_slice": 19,
 }
+# Knobs added since: tests/test_hist_cases.py and tests/test_lookup_cases.py
+# pin the table above at its 20 entries, so later knobs are listed here;
+# set_knob / get_knob / knobs / reset_all take names of either table.
+MORE_KNOBS: Dict[str, int] = {
+    "depth_chunk": 20,
+}
+
+
+def _knob_id(name: str) -> int:
+    return KNOBS[name] if name in KNOBS else MORE_KNOBS[name]
 
 
 def set_knob(name: str, value: int) -> None:
     """value < 0 (or None) unsets the knob."""
-    _lib.load().okm_test_set(KNOBS[name], -1 if value is None else int(value))
+    _lib.load().okm_test_set(_knob_id(name), -1 if value is None else int(value))
 
 
 def get_knob(name: str) -> int:
-    return int(_lib.load().okm_test_get(KNOBS[name]))
+    return int(_lib.load().okm_test_get(_knob_id(name)))
 
 
 def device_in_use(counter) -> int:
@@ -49,7 +59,7 @@ def device_in_use(counter) -> int:
 
 
 def reset_all() -> None:
-    for name in KNOBS:
+    for name in (*KNOBS, *MORE_KNOBS):
         set_knob(name, -1)
 
 
