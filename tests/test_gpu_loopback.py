@@ -10,7 +10,6 @@ rank order must equal the oracle's table of the whole input, exactly.  Sets
 (build.rs:46-58) and the distributed compare (compare.rs:51-66) likewise."""
 
 import os
-import threading
 
 import numpy as np
 import pytest
@@ -18,40 +17,11 @@ import pytest
 import okm
 from okm import testing
 from oracle import OracleCounter
+# a rank that never reaches a collective ends it after a minute, not five
+# (_loopback_timeout: an autouse fixture of every module that imports it)
+from loopback_ranks import _loopback_timeout, run_ranks  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-# a rank that never reaches a collective ends it after a minute, not five
-
-
-@pytest.fixture(autouse=True)
-def _loopback_timeout():
-    """A rank that never arrives ends a collective after 60 s, not 300 (the
-    conftest resets every knob after each test)."""
-    testing.set_knob("loopback_timeout_ms", 60_000)
-    yield
-
-
-def run_ranks(P, fn):
-    """fn(rank) on P threads (one per virtual rank); returns the results in
-    rank order, re-raising the first exception."""
-    out, err = [None] * P, [None] * P
-
-    def body(r):
-        try:
-            out[r] = fn(r)
-        except BaseException as e:  # surfaced below
-            err[r] = e
-
-    th = [threading.Thread(target=body, args=(r,), daemon=True) for r in range(P)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(timeout=600)
-        assert not t.is_alive(), "a virtual rank hung"
-    for e in err:
-        if e is not None:
-            raise e
-    return out
 
 
 def _records(n, genome, seed, hot_every=0, read_len=150):

@@ -340,17 +340,8 @@ def test_empty_gz_output_is_valid_gzip(tmp_path, no_libdeflate):
 # multi-GPU owner split (okm_owner_bounds: host code of okm_merge_owned)
 # ---------------------------------------------------------------------------
 
-def _owner_bounds_np(hist, world):
-    """Restatement: cut r just past the bin where the running total first
-    reaches r/world of the whole (okm_dist.hip owner_bounds)."""
-    cum = np.cumsum(np.asarray(hist, dtype=np.float64))
-    total = cum[-1] if len(cum) else 0.0
-    b = [0]
-    for r in range(1, world):
-        x = int(np.searchsorted(cum, total * r / world, side="left")) + 1
-        b.append(max(b[-1], min(x, len(hist))))
-    b.append(len(hist))
-    return b
+# the numpy restatement of okm_dist.hip owner_bounds (one copy, shared with the exchange cases)
+from exchange_cases import owner_bounds_np as _owner_bounds_np  # noqa: E402
 
 
 @pytest.mark.parametrize("world", [1, 2, 3, 4, 7, 8, 16])
