@@ -238,6 +238,33 @@ okm_status okm_read_depths(okm_ctx *ctx, const uint8_t *seq, const uint64_t *off
 okm_status okm_read_depths_device(okm_ctx *ctx, const uint8_t *d_seq, uint64_t n_bytes, uint64_t n_records,
                                   uint64_t min_count, okm_read_depth *d_out /* device, n_records */);
 
+/* Two counted tables compared: the keys both hold, with their counts -- what
+ * `kmc_tools simple intersect` with counters_min, or two jellyfish tables,
+ * answer; an extension, the reference's compare works on keys alone.  An entry
+ * is "kept" when its count is at least its side's min_count (0 behaves as 1);
+ * a key is shared when it is kept in both tables.  Everything else follows on
+ * the host:
+ *   union             = n_a + n_b - n_shared        (Jaccard = n_shared / union)
+ *   sum of max        = sum_a + sum_b - sum_min     (weighted Jaccard = sum_min / sum of max)
+ *   Bray-Curtis       = 1 - 2 * sum_min / (sum_a + sum_b)
+ *   containment of a  = n_shared / n_a
+ * Both contexts are counted first if batches are pending (as okm_result_size).
+ * Read-only, like okm_lookup_counts: both tables stay where and as they lie (a
+ * count's per-item runs are merged in place, a host-resident table goes up in
+ * slices), the two sorted tables are merged, not searched key by key.  a == b
+ * is allowed (n_shared = n_a); an empty table gives zeros on its side and zero
+ * shared.  A set-mode context on either side: OKM_E_STATE.  Contexts of
+ * different k, width (k > 32 or not) or device, or a null argument: OKM_E_ARG. */
+typedef struct okm_count_compare {
+    uint64_t n_a, n_b;                   /* kept entries of each table */
+    uint64_t sum_a, sum_b;               /* sum of the kept entries' counts, modulo 2^64 */
+    uint64_t n_shared;                   /* keys kept in both tables */
+    uint64_t sum_min;                    /* over shared keys: sum of min(count_a, count_b), modulo 2^64 */
+    uint64_t sum_a_shared, sum_b_shared; /* over shared keys: sum of count_a / of count_b, modulo 2^64 */
+} okm_count_compare;
+okm_status okm_compare_counts(okm_ctx *a, okm_ctx *b, uint64_t min_count_a, uint64_t min_count_b,
+                              okm_count_compare *out);
+
 /* Device pointers to the counted, sorted, unfiltered table (valid until the
  * next add/reset/destroy). */
 okm_status okm_result_device(okm_ctx *ctx, const uint64_t **d_keys, const uint64_t **d_counts,

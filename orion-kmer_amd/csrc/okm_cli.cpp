@@ -219,7 +219,7 @@ static const char *kVersion = "orion-kmer 0.1.0";
 
 static void print_help(const std::string &cmd) {
     if (cmd == "count")
-        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n      --depth <FASTX>              Take the k-mer depth of every record of FASTX in the whole table (extension)\n      --depth-output <FILE>        Where --depth writes id<TAB>windows<TAB>present<TAB>solid<TAB>sum<TAB>min<TAB>max, in input order\n      --depth-min-count <N>        A window is solid when its k-mer's count is at least N [default: 2]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
+        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n      --depth <FASTX>              Take the k-mer depth of every record of FASTX in the whole table (extension)\n      --depth-output <FILE>        Where --depth writes id<TAB>windows<TAB>present<TAB>solid<TAB>sum<TAB>min<TAB>max, in input order\n      --depth-min-count <N>        A window is solid when its k-mer's count is at least N [default: 2]\n      --compare <FASTX>            Count FASTX as a second table (same k) and compare the two tables with their counts (extension)\n      --compare-output <FILE>      Where --compare writes field<TAB>value: the shared k-mers, their counts, Jaccard, weighted Jaccard, Bray-Curtis\n      --compare-min-count <N>      Minimum count of a k-mer of the --compare table (--min-count: of the first table) [default: 1]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
     else if (cmd == "build")
         printf("Build a unique k-mer database from genome assemblies\n\nUsage: orion-kmer build [OPTIONS] --kmer-size <KMER_SIZE> --genomes <GENOME_FILES>... --output-file <OUTPUT_FILE>\n");
     else if (cmd == "compare")
@@ -437,6 +437,46 @@ static int write_depths(okm_group *grp, okm_reader *r, const std::string &path, 
     return 0;
 }
 
+// --compare: the second input counted into a context of its own beside the
+// first table's (one GPU), okm_compare_counts of the two, and field<TAB>value
+// lines: the eight fields, then the ratios that follow from them, printed with
+// four decimals as the reference prints its floats (0 where nothing is kept).
+struct CompareCtx {
+    okm_ctx *c = nullptr;
+    ~CompareCtx() { okm_destroy(c); }
+};
+
+static int write_compare(okm_ctx *first, uint8_t k, bool wide, const std::string &path, const std::string &out_path,
+                         uint64_t min_a, uint64_t min_b) {
+    CompareCtx second;
+    int rc = open_engine(&second.c, k, (okm_mode)(OKM_MODE_COUNT | (wide ? OKM_MODE_WIDE : 0)));
+    if (rc) return rc;
+    if ((rc = feed_file(second.c, path, true, "Failed to get input reader for compare file: "))) return rc;
+    okm_count_compare cc;
+    if (!first || okm_compare_counts(first, second.c, min_a, min_b, &cc) != OKM_OK)
+        return die("GPU engine failure while comparing the tables: " + err_detail());
+    std::string lines;
+    const std::pair<const char *, uint64_t> fields[] = {
+        {"n_a", cc.n_a},         {"n_b", cc.n_b},         {"sum_a", cc.sum_a},
+        {"sum_b", cc.sum_b},     {"n_shared", cc.n_shared}, {"sum_min", cc.sum_min},
+        {"sum_a_shared", cc.sum_a_shared}, {"sum_b_shared", cc.sum_b_shared}};
+    for (auto &f : fields) lines += std::string(f.first) + '\t' + std::to_string(f.second) + '\n';
+    const long double uni = (long double)cc.n_a + cc.n_b - cc.n_shared;
+    const long double tot = (long double)cc.sum_a + cc.sum_b, smax = tot - cc.sum_min;
+    const std::pair<const char *, long double> ratios[] = {
+        {"jaccard", uni > 0 ? cc.n_shared / uni : 0},
+        {"weighted_jaccard", smax > 0 ? cc.sum_min / smax : 0},
+        {"bray_curtis", tot > 0 ? 1 - 2 * (long double)cc.sum_min / tot : 0}};
+    char buf[64];
+    for (auto &r : ratios) {
+        snprintf(buf, sizeof(buf), "%s\t%.4Lf\n", r.first, r.second);
+        lines += buf;
+    }
+    if (okm_write_file(out_path.c_str(), reinterpret_cast<const uint8_t *>(lines.data()), lines.size()) != OKM_OK)
+        return die("Failed to get output writer for compare output file: " + dbg_path(out_path));
+    return 0;
+}
+
 // count.rs:40-141
 static int run_count(const Args &a) {
     uint8_t k;
@@ -476,6 +516,22 @@ static int run_count(const Args &a) {
     uint64_t depth_min = 2;
     if (get_one(a, "depth-min-count", dm) && (!parse_u64(dm, depth_min) || depth_min == 0))
         return usage_error("invalid value '" + dm + "' for '--depth-min-count <N>'");
+    // --compare <FASTX> --compare-output <FILE> [--compare-min-count <N>]: FASTX
+    // is counted at the same k into a second table and the two tables are
+    // compared with their counts (kmc_tools intersect with counters_min; an
+    // extension); --min-count applies to the first table, --compare-min-count
+    // to the second; each of the two flags needs the other.  One GPU only: two
+    // groups' owner splits differ.
+    std::string cmp_path, cmp_out, cm;
+    const bool want_cmp = get_one(a, "compare", cmp_path);
+    if (want_cmp != get_one(a, "compare-output", cmp_out))
+        return usage_error(std::string("the following required arguments were not provided:\n  ") +
+                           (want_cmp ? "--compare-output <FILE>" : "--compare <FASTX>"));
+    uint64_t cmp_min = 1;
+    if (get_one(a, "compare-min-count", cm) && !parse_u64(cm, cmp_min))
+        return usage_error("invalid value '" + cm + "' for '--compare-min-count <N>'");
+    if (want_cmp && g_gpus != 1)
+        return usage_error("the argument '--compare <FASTX>' cannot be used with '--gpus <GPUS>' other than 1");
     // --wide: opt-in two-u64 keys for k in 33..64 (not in the reference, whose
     // error for k > 32 is kept byte-identical without it)
     std::string wflag;
@@ -545,6 +601,11 @@ static int run_count(const Args &a) {
         if ((rc = write_depths(grp, depth_reader.r, depth_path, depth_out, depth_min))) return rc;
         info("orion_kmer::commands::count", "Successfully wrote the read depths to " + dbg_path(depth_out));
         phase("depth");
+    }
+    if (want_cmp) {  // both tables are merged as their counts left them
+        if ((rc = write_compare(okm_group_owner(grp, 0), k, wide, cmp_path, cmp_out, min_count, cmp_min))) return rc;
+        info("orion_kmer::commands::count", "Successfully wrote the table comparison to " + dbg_path(cmp_out));
+        phase("compare");
     }
     okm_status s = okm_group_write_counts_tsv(grp, out.c_str(), min_count, nullptr);
     phase("written");
@@ -1098,6 +1159,9 @@ int main(int argc, char **argv) {
         spec.push_back({"depth", 0, true, false});
         spec.push_back({"depth-output", 0, true, false});
         spec.push_back({"depth-min-count", 0, true, false});
+        spec.push_back({"compare", 0, true, false});
+        spec.push_back({"compare-output", 0, true, false});
+        spec.push_back({"compare-min-count", 0, true, false});
     } else if (cmd == "build") {
         spec.push_back({"kmer-size", 'k', true, false});
         spec.push_back({"genomes", 'g', true, true});

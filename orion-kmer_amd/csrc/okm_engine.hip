@@ -3634,6 +3634,164 @@ okm_status okm_lookup_counts(okm_ctx *c, const uint64_t *keys, uint64_t n, uint6
     return OKM_OK;
 }
 
+// Two counted tables merged in the representations they lie in.  Each side is
+// read through a run list (CmpView): the pending per-item runs behind the
+// index launch_lookup_index builds, or a dense device table -- or one uploaded
+// slice of a host-resident one -- cut into pieces by launch_compare_cut.  The
+// side with more entries drives the merge (okm_compare.hip), and the shared
+// sums are swapped back to (a, b) at the end.  Host-resident tables go up in
+// slices as the lookup's do; with both sides host-resident the slices nest:
+// the shared sums of disjoint key slices add, each side's totals are taken
+// once (a's with every slice of a, b's during a's first slice).  All scratch
+// comes from a's pool and runs on a's stream; b's stream is drained first.
+namespace {
+struct CmpSide {
+    okm_ctx *t;
+    bool pending = false, sliced = false;
+    uint64_t sl = 0, nslices = 0;  // entries per slice; an empty table has no slice
+    unsigned long long *pos = nullptr, *stmp = nullptr, *n_desc = nullptr;
+    uint64_t *first = nullptr, *tk = nullptr, *tc = nullptr;
+    LookItem *desc = nullptr;
+    CmpView v;
+    uint32_t T;  // the call's tile (compare_tile): a dense table is cut into pieces of it
+    CmpSide(okm_ctx *c, uint32_t tile) : t(c), T(tile) {
+        if (!c->n_res) return;
+        pending = c->pend.on;
+        sliced = !pending && c->res_host;
+        sl = c->n_res;
+        if (sliced) {
+            sl = uint64_t(1) << 26;
+            if (const int64_t e = test_knob(OKM_TEST_HIST_SLICE); e > 0) sl = (uint64_t)e;  // tests: several / ragged slices
+            sl = std::min(sl, c->n_res);
+        }
+        nslices = (c->n_res + sl - 1) / sl;
+        v.max_runs = pending ? c->pend.nitems : (uint32_t)((sl + T - 1) / T);
+        v.narrow = pending && c->pend.narrow;
+    }
+    uint64_t slice_len(uint64_t si) const { return std::min(sl, t->n_res - si * sl); }
+    double slice_bytes(uint64_t si) const { return (8.0 * t->kw + (v.narrow ? 4.0 : 8.0)) * (double)slice_len(si); }
+    okm_status prepare(Blocks &scratch) {
+        if (!nslices) return OKM_OK;
+        const uint64_t kw = t->kw, nr = v.max_runs;
+        if (pending) {
+            OKM_TRY(scratch.get((size_t)nr + 1, &pos));
+            OKM_TRY(scratch.get(scan_tmp_elems(nr + 1), &stmp));
+            n_desc = pos + nr;
+        } else {
+            OKM_TRY(scratch.get(1, &n_desc));
+        }
+        OKM_TRY(scratch.get((size_t)nr * kw, &first));
+        OKM_TRY(scratch.get((size_t)nr, &desc));
+        if (sliced) {
+            OKM_TRY(scratch.get(sl * kw, &tk));
+            OKM_TRY(scratch.get(sl, &tc));
+        }
+        v.first = first;
+        v.desc = desc;
+        v.n_desc = n_desc;
+        return OKM_OK;
+    }
+    okm_status upload(hipStream_t s, uint64_t si) {
+        if (!sliced) return OKM_OK;
+        const uint64_t o = si * sl, len = slice_len(si), kw = t->kw;
+        HIP_TRY(hipMemcpyAsync(tk, t->res_keys + o * kw, len * kw * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(tc, t->res_counts + o, len * 8, hipMemcpyHostToDevice, s));
+        return OKM_OK;
+    }
+    // slice si as a run list
+    void index(hipStream_t s, uint64_t si) {
+        v.n = slice_len(si);
+        if (pending) {
+            v.counts = t->pend.sc;
+            launch_lookup_index(s, t->pend.items, t->pend.nitems, t->pend.n_out, t->pend.sk, t->wide, pos, stmp, first,
+                                desc);
+        } else {
+            v.counts = sliced ? tc : t->res_counts;
+            launch_compare_cut(s, sliced ? tk : t->res_keys, v.n, t->wide, T, first, desc, n_desc);
+        }
+    }
+};
+}  // namespace
+
+okm_status okm_compare_counts(okm_ctx *a, okm_ctx *b, uint64_t min_count_a, uint64_t min_count_b,
+                              okm_count_compare *out) {
+    if (!a || !b || !out) return fail(OKM_E_ARG, "okm_compare_counts: null argument");
+    if (a->mode == OKM_MODE_SET || b->mode == OKM_MODE_SET)
+        return fail(OKM_E_STATE, "okm_compare_counts: a set-mode context has no counts");
+    if (a->k != b->k || a->wide != b->wide)
+        return fail(OKM_E_ARG, "okm_compare_counts: the contexts differ in k or in key width");
+    if (a->device != b->device) return fail(OKM_E_ARG, "okm_compare_counts: the contexts are on different devices");
+    *out = okm_count_compare{};
+    min_count_a = std::max<uint64_t>(min_count_a, 1);
+    min_count_b = std::max<uint64_t>(min_count_b, 1);
+    HIP_TRY(hipSetDevice(a->device));
+    OKM_TRY(okm_count(a, nullptr));
+    if (b != a) {
+        OKM_TRY(okm_count(b, nullptr));
+        OKM_TRY(sync(b));  // its table is read from a's stream
+    }
+    hipStream_t s = a->stream;
+    Blocks scratch(*a->pool);
+    unsigned long long *acc = nullptr;  // shared: n | sum_min | sum_d | sum_s; then a's n | sum, b's n | sum
+    OKM_TRY(scratch.get(8, &acc));
+    HIP_TRY(hipMemsetAsync(acc, 0, 8 * sizeof(unsigned long long), s));
+    const uint32_t tile = compare_tile(a->wide);
+    CmpSide A(a, tile), B(b, tile);
+    OKM_TRY(A.prepare(scratch));
+    OKM_TRY(B.prepare(scratch));
+    const bool a_drives = a->n_res >= b->n_res;
+    CmpSide &D = a_drives ? A : B, &S = a_drives ? B : A;
+    unsigned long long *toff = nullptr, *ttmp = nullptr, *slots = nullptr;
+    CmpTile *tiles = nullptr;
+    if (S.nslices) {  // (then D has entries too)
+        OKM_TRY(scratch.get(compare_slot_words(), &slots));
+        HIP_TRY(hipMemsetAsync(slots, 0, compare_slot_words() * sizeof(unsigned long long), s));
+        OKM_TRY(scratch.get((size_t)D.v.max_runs + 1, &toff));
+        OKM_TRY(scratch.get(scan_tmp_elems((uint64_t)D.v.max_runs + 1), &ttmp));
+        OKM_TRY(scratch.get(compare_max_tiles(D.sl, D.v.max_runs, tile), &tiles));
+    }
+    const bool has_a = A.nslices > 0, has_b = B.nslices > 0;
+    for (uint64_t si = 0; si < std::max<uint64_t>(A.nslices, 1); ++si) {
+        for (uint64_t sj = 0; sj < std::max<uint64_t>(B.nslices, 1); ++sj) {
+            const bool a_new = has_a && sj == 0;                          // a's slice si: index it, take its totals
+            const bool b_new = has_b && (si == 0 || B.nslices > 1);       // a device-resident b is indexed once
+            if (a_new) OKM_TRY(A.upload(s, si));
+            if (b_new) OKM_TRY(B.upload(s, sj));
+            a->timer.begin(s);
+            double bytes = 0;  // the keys and counts of both tables, once each
+            if (a_new) {
+                A.index(s, si);
+                launch_compare_totals(s, A.v, min_count_a, acc + 4);
+                bytes += A.slice_bytes(si);
+            }
+            if (b_new) B.index(s, sj);
+            if (has_b && si == 0) {
+                launch_compare_totals(s, B.v, min_count_b, acc + 6);
+                bytes += B.slice_bytes(sj);
+            }
+            if (has_a && has_b)
+                launch_compare(s, D.v, S.v, a->wide, a_drives ? min_count_a : min_count_b,
+                               a_drives ? min_count_b : min_count_a, toff, ttmp, tiles, slots);
+            if (slots && si + 1 == A.nslices && sj + 1 == B.nslices) launch_compare_fold(s, slots, acc);
+            a->timer.end(s, "compare_counts", bytes);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, acc, sizeof(h), hipMemcpyDeviceToHost, s));
+    OKM_TRY(sync(a));
+    scratch.free_all();
+    out->n_shared = h[0];
+    out->sum_min = h[1];
+    out->sum_a_shared = a_drives ? h[2] : h[3];
+    out->sum_b_shared = a_drives ? h[3] : h[2];
+    out->n_a = h[4];
+    out->sum_a = h[5];
+    out->n_b = h[6];
+    out->sum_b = h[7];
+    return OKM_OK;
+}
+
 // Per-record depths of reads against the table in the representation it lies
 // in, as okm_lookup_counts searches it: the pending per-item runs behind a
 // first-key index built once per call, a dense device table, or a

@@ -350,6 +350,45 @@ void launch_lookup_dense(void *stream, const uint64_t *keys, const uint64_t *cou
                          const uint64_t *queries, uint64_t nq, uint64_t *out, unsigned long long *found,
                          bool hits_only);
 
+// Count compare (okm_compare.hip): two counted tables merged where they lie.
+// Every representation is read through a run list, as launch_lookup_index
+// builds it for a pending table; launch_compare_cut writes the same arrays for
+// a dense table keys[n] (pieces of `tile` entries, the call's compare_tile: first and desc
+// hold ceil(n / tile) entries, *n_desc receives that number).
+struct CmpView {
+    const uint64_t *first = nullptr;              // the first key of every run
+    const LookItem *desc = nullptr;
+    const unsigned long long *n_desc = nullptr;   // device: runs
+    const uint64_t *counts = nullptr;             // run r's counts at counts[desc[r].coff] (u32 words when narrow)
+    bool narrow = false;
+    uint32_t max_runs = 0;                        // the host's bound of *n_desc
+    uint64_t n = 0;                               // entries
+};
+// One tile of the driving table and the range of the other table under its key span (k_cmp_bounds).
+struct CmpTile {
+    uint32_t d_run, d_len;
+    uint64_t d_off;
+    uint32_t s_run0, s_run1;
+    uint64_t s_off0, s_off1;
+};
+uint32_t compare_tile(bool wide);
+uint64_t compare_max_tiles(uint64_t n, uint32_t max_runs, uint32_t tile);
+void launch_compare_cut(void *stream, const uint64_t *keys, uint64_t n, bool wide, uint32_t tile, uint64_t *first,
+                        LookItem *desc, unsigned long long *n_desc);
+// out[0] += entries of v with count >= min_count, out[1] += the sum of their counts (mod 2^64).
+void launch_compare_totals(void *stream, const CmpView &v, uint64_t min_count, unsigned long long *out);
+// Over the keys in both d and s whose counts pass min_d / min_s: their
+// number, sum of min(count_d, count_s), sum of count_d, sum of count_s, added
+// into words 0..3 of one of the slots of out (compare_slot_words() words,
+// zeroed by the caller; any number of launches add into them);
+// launch_compare_fold then adds the slots' sums to out4[0..3].  d drives (the larger table).  Scratch:
+// toff = d.max_runs + 1 words, scan_tmp = scan_tmp_elems(d.max_runs + 1),
+// tiles = compare_max_tiles(d.n, d.max_runs, compare_tile(wide)).
+void launch_compare(void *stream, const CmpView &d, const CmpView &s, bool wide, uint64_t min_d, uint64_t min_s,
+                    unsigned long long *toff, unsigned long long *scan_tmp, CmpTile *tiles, unsigned long long *out);
+size_t compare_slot_words();
+void launch_compare_fold(void *stream, const unsigned long long *slots, unsigned long long *out4);
+
 // Per-record k-mer depth (okm_depth.hip): one scan of a device batch (records
 // joined by separators, 16-byte aligned, n bytes) against one representation
 // of the table; rows[r] accumulates record r's okm_read_depth (r = separators

@@ -420,6 +420,18 @@ class KmerCounter:
               "okm_lookup_counts(device)")
         return found.value
 
+    def compare_counts(self, other: "KmerCounter", min_count: int = 1, other_min_count: int = 1) -> Dict[str, int]:
+        """This table (a) against other's (b), both merged where they lie
+        (okm_compare_counts): {n_a, n_b, sum_a, sum_b, n_shared, sum_min,
+        sum_a_shared, sum_b_shared} over the entries with count >= min_count /
+        other_min_count.  Jaccard = n_shared / (n_a + n_b - n_shared), weighted
+        Jaccard = sum_min / (sum_a + sum_b - sum_min), Bray-Curtis = 1 - 2 *
+        sum_min / (sum_a + sum_b)."""
+        cc = _lib.CountCompare()
+        check(lib().okm_compare_counts(self.ctx, other.ctx, min_count, other_min_count, byref(cc)),
+              "okm_compare_counts")
+        return {f: int(getattr(cc, f)) for f, _ in _lib.CountCompare._fields_}
+
     def read_depths(self, seqs: Sequence[bytes], min_count: int = 2, normalized: bool = False) -> np.ndarray:
         """One row per record (READ_DEPTH_DTYPE: windows, present, solid, sum,
         min, max): how deep the record's k-mers lie in the counted table,
@@ -594,7 +606,12 @@ def distributed_compare(comm: "Comm", a: "KmerCounter", b: "KmerCounter", owner_
     of B meet on one rank; each owner intersects its two ranges on its GPU
     (compare.rs:58) and |A|, |B|, |A ∩ B| are summed over the ranks.  Every
     rank returns the global (|A|, |B|, |A ∩ B|); union and Jaccard follow on
-    the host (compare.rs:60-66)."""
+    the host (compare.rs:60-66).
+
+    Count contexts (of any k) merged under one split in the same way
+    (merge_owned_n) can be compared with their counts per rank by
+    owner_a.compare_counts(owner_b): the owners' key ranges are disjoint, so
+    the eight fields add over the ranks (comm.allreduce)."""
     if any(c.wide for c in (a, b, owner_a, owner_b)):
         # okm_set_intersection_size_device reads plain u64 keys; compare.rs:37-39
         # only ever sees k <= 32 databases (KmerDbV2 stores u64 keys)

@@ -71,6 +71,13 @@ class CountSummary(Structure):
     _fields_ = [("n_distinct", c_uint64), ("n_instances", c_uint64), ("max_count", c_uint64)]
 
 
+class CountCompare(Structure):
+    """okm_count_compare."""
+    _fields_ = [("n_a", c_uint64), ("n_b", c_uint64), ("sum_a", c_uint64), ("sum_b", c_uint64),
+                ("n_shared", c_uint64), ("sum_min", c_uint64), ("sum_a_shared", c_uint64),
+                ("sum_b_shared", c_uint64)]
+
+
 class Key128(Structure):
     """okm_key128: value = hi * 2**64 + lo."""
     _fields_ = [("lo", c_uint64), ("hi", c_uint64)]
@@ -180,6 +187,7 @@ PROTOTYPES = {
     "okm_write_histogram_tsv": (c_int, [c_char_p, c_void_p, c_uint64]),
     "okm_lookup_counts": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_int, _P64]),
     "okm_group_lookup_counts": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, _P64]),
+    "okm_compare_counts": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, POINTER(CountCompare)]),
     "okm_read_depths": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_uint64, c_void_p]),
     "okm_read_depths_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_uint64, c_void_p]),
     "okm_group_read_depths": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_uint64, c_void_p]),

@@ -37,6 +37,11 @@ input, warmup then timed steps bracketed by device syncs).
                      caller did before it: the gather (compact_items) plus
                      torch.searchsorted and an index of the counts; then the
                      same pair over the dense table, without the gather.
+  --workload compare okm_compare_counts of two counted configs[1]-sized tables
+                     (two read seeds of one genome), both pending and both
+                     dense, against the composition used before in the same
+                     process: the gather, okm_lookup_counts of all of A's keys
+                     in B, and a torch reduction; results asserted equal.
   --workload depth   okm_read_depths_device of the configs[1] batch against its
                      own counted table, pending and then dense, and in the same
                      process the yardstick: okm_lookup_counts of 2^24 device
@@ -346,6 +351,108 @@ def wl_lookup(args):
                                                  col("torch_searchsorted_index_ms")["median"], 4)},
             "repeats": rows,
             "roofline": {"bound": "latency (dependent loads of a search)", "kernel": "k_lookup_items<ull, narrow>",
+                         "alg_bytes_per_step": alg, "achieved": round(alg / (pend["median"] * 1e-3) / 1e9, 1),
+                         "peak": HBM_PEAK_GBS, "unit": "GB/s"}}
+
+
+def wl_compare(args):
+    """okm_compare_counts of two counted C2-sized tables (the configs[1] batch
+    and a second batch of the same genome with another read seed) against what
+    a caller composed before: result_device() of A (the gather), lookup_device
+    of all of A's keys in B, B's totals from count_histogram, and a torch
+    reduction of the same eight numbers.  Each repeat counts both batches
+    again (both tables pending), times the in-place compare, then the
+    composition (which leaves A dense), then gathers B and times the compare
+    over two dense tables.  The three results are asserted equal."""
+    import torch
+    k, repeats = 31, 3
+    steps = max(args.steps, 5)
+    bufs = []
+    for seed in (2, 12):
+        b = okm.synth_reads(READS, READ_LEN, genome_len=GENOME_BP, genome_seed=2, seed=seed, sub_rate=0.001, n_rate=0.0001)
+        bufs.append((okm.DeviceBuffer(len(b)), len(b)))
+        bufs[-1][0].upload(b)
+        del b
+
+    def stat(c, name):
+        return dict(c.kernel_stats().get(name, {"launches": 0, "total_ms": 0.0, "alg_bytes": 0.0}))
+
+    def compare_ms(a, b):
+        for _ in range(args.warmup):
+            a.compare_counts(b)
+        s0 = stat(a, "compare_counts")
+        t = time.perf_counter()
+        for _ in range(steps):
+            got = a.compare_counts(b)
+        wall = (time.perf_counter() - t) * 1e3 / steps
+        s1 = stat(a, "compare_counts")
+        assert s1["launches"] - s0["launches"] == steps
+        return (s1["total_ms"] - s0["total_ms"]) / steps, wall, got, (s1["alg_bytes"] - s0["alg_bytes"]) / steps
+
+    rows = []
+    with okm.KmerCounter(k) as a, okm.KmerCounter(k) as b:
+        for rep in range(repeats):
+            for c, (buf, n) in zip((a, b), bufs):
+                c.reset()
+                c.add_device_batch(buf.address, n)
+                c.count()
+                c.set_timing(True)
+            g0 = stat(a, "compact_items")["launches"] + stat(b, "compact_items")["launches"]
+            pend_ms, pend_wall, got, alg = compare_ms(a, b)
+            assert stat(a, "compact_items")["launches"] + stat(b, "compact_items")["launches"] == g0, "the compare gathered"
+            # the composition a caller used before
+            s0 = {n: stat(c, n) for c, n in ((a, "compact_items"), (b, "lookup_counts"), (b, "count_histogram"))}
+            t = time.perf_counter()
+            pk, pc, na = a.result_device()
+            ac = torch.as_tensor(_DevView(pc, na), device="cuda")
+            bc = torch.empty(na, dtype=torch.int64, device="cuda")
+            b.lookup_device(pk, na, bc.data_ptr())
+            _, sm = b.count_histogram(2)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            sh = bc > 0
+            ref = {"n_a": na, "n_b": sm["n_distinct"], "sum_a": int(ac.sum()), "sum_b": sm["n_instances"],
+                   "n_shared": int(sh.sum()), "sum_min": int(torch.minimum(ac, bc).sum()),
+                   "sum_a_shared": int((ac * sh).sum()), "sum_b_shared": int(bc.sum())}
+            e1.record()
+            torch.cuda.synchronize()
+            before_wall = (time.perf_counter() - t) * 1e3
+            parts = {n: stat(c, n)["total_ms"] - s0[n]["total_ms"]
+                     for c, n in ((a, "compact_items"), (b, "lookup_counts"), (b, "count_histogram"))}
+            parts["torch_reduce"] = e0.elapsed_time(e1)
+            assert got == ref, (got, ref)
+            del ac, bc, sh
+            b.result_device()
+            dense_ms, dense_wall, dgot, _ = compare_ms(a, b)
+            assert dgot == ref
+            rows.append({"compare_pending_ms": pend_ms, "compare_pending_wall_ms": pend_wall,
+                         "before_ms": sum(parts.values()), "before_wall_ms": before_wall,
+                         "before_parts_ms": {n: round(v, 4) for n, v in parts.items()},
+                         "compare_dense_ms": dense_ms, "compare_dense_wall_ms": dense_wall})
+            log(json.dumps(rows[-1]))
+    for buf, _ in bufs:
+        buf.free()
+
+    def col(name):
+        v = sorted(r[name] for r in rows)
+        return {"median": round(v[len(v) // 2], 4), "min": round(v[0], 4), "max": round(v[-1], 4)}
+
+    pend, dense, before = col("compare_pending_ms"), col("compare_dense_ms"), col("before_ms")
+    spread = max(pend["max"] - pend["min"], dense["max"] - dense["min"])
+    return {"metric": "two counted C2 tables (k=31) compared with their counts where they lie on one MI355X, HIP-event ms",
+            "value": pend["median"], "unit": "ms", "n_gpus": 1, "steps": steps, "warmup": args.warmup,
+            "higher_is_better": False, "dtype": "u64 keys, u32 staged counts",
+            "data": "synthetic (BASELINE configs[1] reads and a second read seed of the same genome, device-resident)",
+            "config": {"workload": "compare: 2 x 3,355,443 x 150 bp reads counted into two tables", "k": k,
+                       "repeats": repeats, "result": got},
+            "pending": {"compare_ms": pend, "compare_wall_ms": col("compare_pending_wall_ms"), "before_ms": before,
+                        "before_wall_ms": col("before_wall_ms"),
+                        "compare_over_before": round(pend["median"] / before["median"], 4),
+                        "faster_than_before": pend["max"] < before["min"]},
+            "dense": {"compare_ms": dense, "compare_wall_ms": col("compare_dense_wall_ms"), "spread_ms": round(spread, 4),
+                      "no_slower_than_pending": dense["median"] <= pend["median"] + spread},
+            "repeats": rows,
+            "roofline": {"bound": "memory (both tables' keys and counts, once)", "kernel": "compare_counts (all launches)",
                          "alg_bytes_per_step": alg, "achieved": round(alg / (pend["median"] * 1e-3) / 1e9, 1),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s"}}
 
@@ -975,7 +1082,7 @@ def wl_classify(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth"],
+    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth", "compare"],
                     required=True)
     ap.add_argument("--no-ref", action="store_true", help="c3: skip the one-GPU reference table")
     ap.add_argument("--c3-reads", type=int, default=C3_READS,
@@ -999,7 +1106,8 @@ def main():
             testing.set_knob(name, int(val))
     c5 = wl_c5_dist if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.loopback else wl_c5
     out = {"query": wl_query, "build": wl_build, "wide": wl_wide, "classify": wl_classify,
-           "c5": c5, "c3": wl_c3_loop, "histogram": wl_histogram, "lookup": wl_lookup, "depth": wl_depth}[args.workload](args)
+           "c5": c5, "c3": wl_c3_loop, "histogram": wl_histogram, "lookup": wl_lookup, "depth": wl_depth,
+           "compare": wl_compare}[args.workload](args)
     if out is not None:
         print(json.dumps(out), flush=True)
 
