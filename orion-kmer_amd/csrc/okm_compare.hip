@@ -5,8 +5,8 @@
 // Both tables are sorted by key, so the comparison is a merge, not a search
 // per key: every entry of either table is read from memory once.
 //
-// One view for every representation: a run list (the first key of every run,
-// a LookItem per run, the number of runs on the device).  For a count's pending
+// One view for every representation: a TableView's run list (the first key of
+// every run, a LookItem per run, the number of runs on the device).  For a count's pending
 // per-item runs it is what launch_lookup_index builds; a dense table (or one
 // uploaded slice of a host-resident one) is cut into pieces of one tile by
 // k_cmp_cut.  The kernels below have one form per key type and count width, not
@@ -350,7 +350,7 @@ void launch_compare_cut(void *stream, const uint64_t *keys, uint64_t n, bool wid
                            reinterpret_cast<ull *>(first), desc, n_desc);
 }
 
-void launch_compare_totals(void *stream, const CmpView &v, uint64_t min_count, unsigned long long *out) {
+void launch_compare_totals(void *stream, const TableView &v, uint64_t min_count, unsigned long long *out) {
     if (!v.max_runs) return;
     const dim3 g(v.max_runs < 2048u ? v.max_runs : 2048u), b(kCmpBlock);
     hipStream_t s = (hipStream_t)stream;
@@ -361,7 +361,7 @@ void launch_compare_totals(void *stream, const CmpView &v, uint64_t min_count, u
 }
 
 template <typename KT>
-static void compare_tiles(hipStream_t s, const CmpView &d, const CmpView &sv, uint64_t min_d, uint64_t min_s,
+static void compare_tiles(hipStream_t s, const TableView &d, const TableView &sv, uint64_t min_d, uint64_t min_s,
                           const unsigned long long *toff, CmpTile *tiles, unsigned long long *out) {
     const uint32_t T = compare_tile(sizeof(KT) == 16);
     const uint64_t max_tiles = compare_max_tiles(d.n, d.max_runs, T);
@@ -383,7 +383,7 @@ static void compare_tiles(hipStream_t s, const CmpView &d, const CmpView &sv, ui
 #undef OKM_CMP_LAUNCH
 }
 
-void launch_compare(void *stream, const CmpView &d, const CmpView &sv, bool wide, uint64_t min_d, uint64_t min_s,
+void launch_compare(void *stream, const TableView &d, const TableView &sv, bool wide, uint64_t min_d, uint64_t min_s,
                     unsigned long long *toff, unsigned long long *scan_tmp, CmpTile *tiles, unsigned long long *out) {
     if (!d.max_runs || !sv.max_runs) return;
     hipStream_t s = (hipStream_t)stream;

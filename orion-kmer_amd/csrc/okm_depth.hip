@@ -85,81 +85,6 @@ __global__ __launch_bounds__(kDepthBlock) void k_depth_sep_count(const uint8_t *
     if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
 }
 
-// The table's representations: find() answers kDepthFly windows at once
-// (live[f]: window f is valid), hit[f] and, where hit, its count.
-
-// keys[n] / counts[n], dense (n == 0: an empty table, nothing is read)
-template <typename KT>
-struct DepthDense {
-    const KT *keys;
-    const uint64_t *counts;
-    ull n;
-    __device__ __forceinline__ void begin() {}
-    __device__ __forceinline__ void find(const KT (&q)[kDepthFly], const bool (&live)[kDepthFly],
-                                         ull (&cnt)[kDepthFly], bool (&hit)[kDepthFly]) const {
-        typedef KeyOps<KT> O;
-        FlatKeys<KT> a[kDepthFly];
-        ull len[kDepthFly], pos[kDepthFly];
-        KT last[kDepthFly];
-#pragma unroll
-        for (int f = 0; f < kDepthFly; ++f) {
-            a[f].p = keys;
-            len[f] = live[f] ? n : 0;
-        }
-        search_last_le<KT, kDepthFly>(a, len, q, pos, last);
-#pragma unroll
-        for (int f = 0; f < kDepthFly; ++f) {
-            hit[f] = len[f] && O::eq(last[f], q[f]);
-            cnt[f] = hit[f] ? counts[pos[f]] : 0;
-        }
-    }
-};
-
-// The pending per-item runs behind launch_lookup_index's first-key index, as
-// k_lookup_items searches them; NARROW: the runs' counts are u32.
-template <typename KT, bool NARROW>
-struct DepthItems {
-    const KT *first;
-    const LookItem *desc;
-    const ull *n_desc;
-    const uint64_t *sc;
-    ull m;
-    __device__ __forceinline__ void begin() { m = *n_desc; }
-    __device__ __forceinline__ void find(const KT (&q)[kDepthFly], const bool (&live)[kDepthFly],
-                                         ull (&cnt)[kDepthFly], bool (&hit)[kDepthFly]) const {
-        typedef KeyOps<KT> O;
-        FlatKeys<KT> a[kDepthFly];
-        ull len[kDepthFly], pos[kDepthFly], coff[kDepthFly];
-        KT last[kDepthFly];
-#pragma unroll
-        for (int f = 0; f < kDepthFly; ++f) {
-            a[f].p = first;
-            len[f] = live[f] ? m : 0;
-        }
-        // the item whose first key is the last one <= the window's key
-        search_last_le<KT, kDepthFly>(a, len, q, pos, last);
-#pragma unroll
-        for (int f = 0; f < kDepthFly; ++f) {
-            const bool owned = len[f] && !O::lt(q[f], last[f]);  // else: below the table's first key
-            len[f] = 0;
-            coff[f] = 0;
-            if (owned) {
-                const LookItem *d = desc + pos[f];
-                a[f].p = reinterpret_cast<const KT *>(gload(&d->keys));
-                coff[f] = gload(&d->coff);
-                len[f] = gload(&d->n);
-            }
-        }
-        search_last_le<KT, kDepthFly>(a, len, q, pos, last);
-        const uint32_t *sc32 = reinterpret_cast<const uint32_t *>(sc);
-#pragma unroll
-        for (int f = 0; f < kDepthFly; ++f) {
-            hit[f] = len[f] && O::eq(last[f], q[f]);
-            cnt[f] = !hit[f] ? 0 : NARROW ? (ull)sc32[coff[f] + pos[f]] : (ull)sc[coff[f] + pos[f]];
-        }
-    }
-};
-
 // A key type's side of the scan: the halo its windows need, the valid windows
 // of the thread's run and the canonical key of window j.
 template <typename KT> struct DepthKeys;
@@ -311,22 +236,22 @@ static void launch_depth_tab(hipStream_t s, uint32_t ntiles, const uint8_t *seq,
 
 template <typename KT>
 static void launch_depth_key(hipStream_t s, uint32_t ntiles, const uint8_t *seq, uint64_t n, const ull *pre,
-                             const DepthTable &t, uint32_t k, uint64_t min_count, bool count_windows, ull *rows,
+                             const TableView &t, uint32_t k, uint64_t min_count, bool count_windows, ull *rows,
                              uint64_t nrec) {
-    if (!t.items) {
-        const DepthDense<KT> tab{reinterpret_cast<const KT *>(t.keys), t.counts, t.n};
+    if (!t.runs) {
+        const FindDense<KT, kDepthFly> tab{reinterpret_cast<const KT *>(t.keys), t.counts, t.n};
         launch_depth_tab<KT>(s, ntiles, seq, n, pre, tab, k, min_count, count_windows, rows, nrec);
     } else if (t.narrow) {
-        const DepthItems<KT, true> tab{reinterpret_cast<const KT *>(t.first), t.desc, t.n_desc, t.sc, 0};
+        const FindItems<KT, true, kDepthFly> tab{reinterpret_cast<const KT *>(t.first), t.desc, t.n_desc, t.counts, 0};
         launch_depth_tab<KT>(s, ntiles, seq, n, pre, tab, k, min_count, count_windows, rows, nrec);
     } else {
-        const DepthItems<KT, false> tab{reinterpret_cast<const KT *>(t.first), t.desc, t.n_desc, t.sc, 0};
+        const FindItems<KT, false, kDepthFly> tab{reinterpret_cast<const KT *>(t.first), t.desc, t.n_desc, t.counts, 0};
         launch_depth_tab<KT>(s, ntiles, seq, n, pre, tab, k, min_count, count_windows, rows, nrec);
     }
 }
 
 void launch_read_depths(void *stream, const uint8_t *seq, uint64_t n, uint64_t nrec, uint32_t k, bool wide,
-                        const DepthTable &t, uint64_t min_count, bool count_windows, unsigned long long *tiles,
+                        const TableView &t, uint64_t min_count, bool count_windows, unsigned long long *tiles,
                         okm_read_depth *rows) {
     if (!n || !nrec) return;
     hipStream_t s = (hipStream_t)stream;

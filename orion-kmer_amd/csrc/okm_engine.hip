@@ -3463,10 +3463,108 @@ okm_status okm_fetch_counts(okm_ctx *c, uint64_t min_count, uint64_t *keys, uint
     return fetch_result(c, min_count, keys, counts, cap, n, dst_on_device != 0);
 }
 
-// The count histogram of the table in the representation it lies in: the
-// pending per-item runs (only their counts are read; no gather, no run block
-// taken), a dense device table, or a host-resident one, whose counts alone go
-// up in slices.  Nothing of the table changes hands.
+// The counted table as it lies, for the readers that leave it there:
+// okm_count_histogram, okm_lookup_counts, okm_read_depths[_device] and
+// okm_compare_counts.  It lies in one of three representations: the count's
+// pending per-item runs, a dense device table, or a host-resident table,
+// which goes up in slices of 2^26 entries through one pair of scratch buffers
+// (slice i + 1's copy queues behind slice i's kernels).  A reader walks
+//   for si < nslices:  upload(si)  [its timer bracket:]  index(si)  its kernels on view(si)
+// and nothing of the table changes hands.  The form its kernels read decides
+// the scratch:
+//   Counts  the counts alone: no index of a pending table, no keys of a slice
+//   Search  a pending table through its first-key index (launch_lookup_index:
+//           built in scratch, once per call), the others flat
+//   Runs    every representation as a run list: the index again, or the flat
+//           keys of a slice cut into pieces of `tile` (launch_compare_cut)
+// An empty table is none of the three: no slice, no scratch, a view of no
+// entries; what a reader does then is its own rule.
+namespace {
+enum class TableForm { Counts, Search, Runs };
+
+struct TableReader {
+    okm_ctx *t;
+    uint32_t tile;                        // Runs: the piece a flat table is cut into
+    bool pending, sliced, runs, keys_up;  // runs: the views are run lists; keys_up: a slice's keys go up too
+    uint64_t sl, nslices;                 // entries per slice (the last may hold fewer)
+    uint32_t max_runs = 0;                // the run list's bound: first / desc hold as many
+    bool indexed = false;
+    unsigned long long *pos = nullptr, *stmp = nullptr, *n_desc = nullptr;
+    uint64_t *first = nullptr, *tk = nullptr, *tc = nullptr;
+    LookItem *desc = nullptr;
+    TableReader(okm_ctx *c, TableForm form, uint32_t cut = 0) : t(c), tile(cut), keys_up(form != TableForm::Counts) {
+        pending = c->pend.on && c->n_res;
+        sliced = !pending && c->res_host && c->n_res;
+        runs = c->n_res && keys_up && (pending || form == TableForm::Runs);
+        sl = c->n_res;
+        if (sliced) {
+            sl = uint64_t(1) << 26;
+            if (const int64_t e = test_knob(OKM_TEST_HIST_SLICE); e > 0) sl = (uint64_t)e;  // tests: several / ragged slices
+            sl = std::min(sl, c->n_res);
+        }
+        nslices = c->n_res ? (c->n_res + sl - 1) / sl : 0;
+        if (runs) max_runs = pending ? c->pend.nitems : (uint32_t)((sl + tile - 1) / tile);
+    }
+    uint64_t slice_len(uint64_t si) const { return std::min(sl, t->n_res - si * sl); }
+    okm_status prepare(Blocks &scratch) {
+        const uint64_t kw = t->kw, nr = max_runs;
+        if (runs) {
+            if (pending) {
+                OKM_TRY(scratch.get((size_t)nr + 1, &pos));
+                OKM_TRY(scratch.get(scan_tmp_elems(nr + 1), &stmp));
+                n_desc = pos + nr;
+            } else {
+                OKM_TRY(scratch.get(1, &n_desc));
+            }
+            OKM_TRY(scratch.get((size_t)nr * kw, &first));
+            OKM_TRY(scratch.get((size_t)nr, &desc));
+        }
+        if (sliced) {
+            if (keys_up) OKM_TRY(scratch.get(sl * kw, &tk));
+            OKM_TRY(scratch.get(sl, &tc));
+        }
+        return OKM_OK;
+    }
+    okm_status upload(hipStream_t s, uint64_t si) {
+        if (!sliced) return OKM_OK;
+        const uint64_t o = si * sl, len = slice_len(si), kw = t->kw;
+        if (keys_up) HIP_TRY(hipMemcpyAsync(tk, t->res_keys + o * kw, len * kw * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(tc, t->res_counts + o, len * 8, hipMemcpyHostToDevice, s));
+        return OKM_OK;
+    }
+    // Slice si's run list, where the views are run lists: a pending table's is
+    // built by the first call and stands; a flat slice is cut by every call.
+    void index(hipStream_t s, uint64_t si) {
+        if (!runs) return;
+        if (!pending)
+            launch_compare_cut(s, sliced ? tk : t->res_keys, slice_len(si), t->wide, tile, first, desc, n_desc);
+        else if (!indexed)
+            launch_lookup_index(s, t->pend.items, t->pend.nitems, t->pend.n_out, t->pend.sk, t->wide, pos, stmp, first,
+                                desc);
+        indexed = true;
+    }
+    TableView view(uint64_t si) const {
+        TableView v;
+        v.runs = runs;
+        v.n = slice_len(si);
+        v.first = first;
+        v.desc = desc;
+        v.n_desc = n_desc;
+        v.max_runs = max_runs;
+        if (pending) {
+            v.counts = t->pend.sc;
+            v.narrow = t->pend.narrow;
+        } else {
+            v.keys = sliced ? tk : t->res_keys;
+            v.counts = sliced ? tc : t->res_counts;
+        }
+        return v;
+    }
+};
+}  // namespace
+
+// The count histogram: only the counts are read (TableForm::Counts).  A
+// pending table's are read in its runs, where the count kernels staged them.
 okm_status okm_count_histogram(okm_ctx *c, uint64_t *hist, uint64_t n_bins, okm_count_summary *summary) {
     if (!c || !hist) return fail(OKM_E_ARG, "okm_count_histogram: null argument");
     if (n_bins < 2 || n_bins > (uint64_t(1) << 20) + 1)
@@ -3476,34 +3574,23 @@ okm_status okm_count_histogram(okm_ctx *c, uint64_t *hist, uint64_t n_bins, okm_
     OKM_TRY(okm_count(c, nullptr));
     memset(hist, 0, n_bins * sizeof(uint64_t));
     if (summary) *summary = okm_count_summary{};
-    const uint64_t n = c->n_res;
-    if (n == 0) return OKM_OK;
+    if (c->n_res == 0) return OKM_OK;
     unsigned long long *dh = nullptr;  // n_bins bins, then entries | sum of counts | max count
     Blocks scratch(*c->pool);
     OKM_TRY(scratch.get(n_bins + 3, &dh));
     HIP_TRY(hipMemsetAsync(dh, 0, (n_bins + 3) * sizeof(unsigned long long), c->stream));
-    if (c->pend.on) {
+    TableReader tab(c, TableForm::Counts);
+    OKM_TRY(tab.prepare(scratch));
+    for (uint64_t si = 0; si < tab.nslices; ++si) {
+        OKM_TRY(tab.upload(c->stream, si));
+        const TableView v = tab.view(si);
         c->timer.begin(c->stream);
-        launch_hist_items(c->stream, c->pend.items, c->pend.nitems, c->pend.n_out, c->pend.sc, c->pend.narrow, n_bins,
-                          dh, dh + n_bins);
-        c->timer.end(c->stream, "count_histogram", (c->pend.narrow ? 4.0 : 8.0) * (double)n);
-    } else if (!c->res_host) {
-        c->timer.begin(c->stream);
-        launch_hist_dense(c->stream, c->res_counts, n, n_bins, dh, dh + n_bins);
-        c->timer.end(c->stream, "count_histogram", 8.0 * (double)n);
-    } else {
-        uint64_t sl = uint64_t(1) << 26;
-        if (const int64_t e = test_knob(OKM_TEST_HIST_SLICE); e > 0) sl = (uint64_t)e;  // tests: several / ragged slices
-        sl = std::min(sl, n);
-        uint64_t *dc = nullptr;
-        OKM_TRY(scratch.get(sl, &dc));
-        for (uint64_t o = 0; o < n; o += sl) {  // one buffer: slice i + 1's copy queues behind slice i's kernel
-            const uint64_t len = std::min(sl, n - o);
-            HIP_TRY(hipMemcpyAsync(dc, c->res_counts + o, len * 8, hipMemcpyHostToDevice, c->stream));
-            c->timer.begin(c->stream);
-            launch_hist_dense(c->stream, dc, len, n_bins, dh, dh + n_bins);
-            c->timer.end(c->stream, "count_histogram", 8.0 * (double)len);
-        }
+        if (tab.pending)
+            launch_hist_items(c->stream, c->pend.items, c->pend.nitems, c->pend.n_out, v.counts, v.narrow, n_bins, dh,
+                              dh + n_bins);
+        else
+            launch_hist_dense(c->stream, v.counts, v.n, n_bins, dh, dh + n_bins);
+        c->timer.end(c->stream, "count_histogram", (v.narrow ? 4.0 : 8.0) * (double)v.n);
     }
     HIP_TRY(hipGetLastError());
     unsigned long long sm[3] = {0, 0, 0};
@@ -3519,13 +3606,10 @@ okm_status okm_count_histogram(okm_ctx *c, uint64_t *hist, uint64_t n_bins, okm_
     return OKM_OK;
 }
 
-// The counts of given keys, searched in the representation the table lies in:
-// the pending per-item runs (a first-key index over the items, built in
-// scratch per call, then the item's run), a dense device table, or a
-// host-resident one, which goes up in slices of keys and counts, every slice
-// searched for all queries (a slice writes only the queries it finds).  Host
-// queries go through scratch in chunks of kLookupChunk, so the call's device
-// footprint does not grow with n.  Nothing of the table changes hands.
+// The counts of given keys, searched in the table (TableForm::Search).  Every
+// slice of a host-resident table is searched for all queries and writes only
+// the queries it finds.  Host queries go through scratch in chunks of
+// kLookupChunk, so the call's device footprint does not grow with n.
 constexpr uint64_t kLookupChunk = uint64_t(1) << 22;
 
 okm_status okm_lookup_counts(okm_ctx *c, const uint64_t *keys, uint64_t n, uint64_t *counts, int on_device,
@@ -3537,8 +3621,8 @@ okm_status okm_lookup_counts(okm_ctx *c, const uint64_t *keys, uint64_t n, uint6
     if (n == 0) return OKM_OK;
     HIP_TRY(hipSetDevice(c->device));
     OKM_TRY(okm_count(c, nullptr));
-    const uint64_t nt = c->n_res, kw = c->kw;
-    if (nt == 0) {
+    const uint64_t kw = c->kw;
+    if (c->n_res == 0) {  // an empty table: zeros, before any scratch
         if (!on_device) {
             memset(counts, 0, n * sizeof(uint64_t));
             return OKM_OK;
@@ -3546,29 +3630,13 @@ okm_status okm_lookup_counts(okm_ctx *c, const uint64_t *keys, uint64_t n, uint6
         HIP_TRY(hipMemsetAsync(counts, 0, n * sizeof(uint64_t), c->stream));
         return sync(c);
     }
-    const bool pending = c->pend.on, sliced = !pending && c->res_host;
     Blocks scratch(*c->pool);
     unsigned long long *dfound = nullptr;
     OKM_TRY(scratch.get(1, &dfound));
     HIP_TRY(hipMemsetAsync(dfound, 0, sizeof(unsigned long long), c->stream));
-    // the table's side
-    unsigned long long *pos = nullptr, *stmp = nullptr;
-    uint64_t *first = nullptr, *tk = nullptr, *tc = nullptr;
-    LookItem *desc = nullptr;
-    uint64_t sl = nt;
-    if (pending) {
-        const uint32_t ni = c->pend.nitems;
-        OKM_TRY(scratch.get((size_t)ni + 1, &pos));
-        OKM_TRY(scratch.get(scan_tmp_elems((uint64_t)ni + 1), &stmp));
-        OKM_TRY(scratch.get((size_t)ni * kw, &first));
-        OKM_TRY(scratch.get((size_t)ni, &desc));
-    } else if (sliced) {
-        sl = uint64_t(1) << 26;
-        if (const int64_t e = test_knob(OKM_TEST_HIST_SLICE); e > 0) sl = (uint64_t)e;  // tests: several / ragged slices
-        sl = std::min(sl, nt);
-        OKM_TRY(scratch.get(sl * kw, &tk));
-        OKM_TRY(scratch.get(sl, &tc));
-    }
+    TableReader tab(c, TableForm::Search);
+    OKM_TRY(tab.prepare(scratch));
+    const bool sliced = tab.sliced;
     // the queries' side
     const uint64_t chunk = on_device ? n : std::min(n, kLookupChunk);
     uint64_t *dq = nullptr, *dc = nullptr;
@@ -3583,13 +3651,9 @@ okm_status okm_lookup_counts(okm_ctx *c, const uint64_t *keys, uint64_t n, uint6
     } else if (sliced) {
         HIP_TRY(hipMemsetAsync(counts, 0, n * sizeof(uint64_t), c->stream));
     }
-    bool first_launch = true;
-    for (uint64_t o = 0; o < nt; o += sl) {  // one pass unless the table is host-resident
-        const uint64_t len = std::min(sl, nt - o);
-        if (sliced) {
-            HIP_TRY(hipMemcpyAsync(tk, c->res_keys + o * kw, len * kw * 8, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(tc, c->res_counts + o, len * 8, hipMemcpyHostToDevice, c->stream));
-        }
+    for (uint64_t si = 0; si < tab.nslices; ++si) {
+        OKM_TRY(tab.upload(c->stream, si));
+        const TableView v = tab.view(si);
         for (uint64_t qo = 0; qo < n; qo += chunk) {
             const uint64_t nq = std::min(chunk, n - qo);
             const uint64_t *q = keys + qo * kw;
@@ -3601,19 +3665,10 @@ okm_status okm_lookup_counts(okm_ctx *c, const uint64_t *keys, uint64_t n, uint6
                 out = dc;
             }
             c->timer.begin(c->stream);
-            if (pending) {
-                if (first_launch)
-                    launch_lookup_index(c->stream, c->pend.items, c->pend.nitems, c->pend.n_out, c->pend.sk, c->wide, pos,
-                                        stmp, first, desc);
-                launch_lookup_items(c->stream, first, desc, pos + c->pend.nitems, c->pend.sc, c->pend.narrow, c->wide,
-                                    q, nq, out, dfound);
-            } else {
-                launch_lookup_dense(c->stream, sliced ? tk : c->res_keys, sliced ? tc : c->res_counts, len, c->wide, q,
-                                    nq, out, dfound, sliced);
-            }
+            tab.index(c->stream, si);
+            launch_lookup(c->stream, v, c->wide, q, nq, out, dfound, sliced);
             // the queries in and the counts out, once per query however many slices search it
-            c->timer.end(c->stream, "lookup_counts", o == 0 ? (8.0 * kw + 8.0) * (double)nq : 0.0);
-            first_launch = false;
+            c->timer.end(c->stream, "lookup_counts", si == 0 ? (8.0 * kw + 8.0) * (double)nq : 0.0);
             HIP_TRY(hipGetLastError());
             if (on_device) continue;
             if (!sliced) {
@@ -3634,85 +3689,14 @@ okm_status okm_lookup_counts(okm_ctx *c, const uint64_t *keys, uint64_t n, uint6
     return OKM_OK;
 }
 
-// Two counted tables merged in the representations they lie in.  Each side is
-// read through a run list (CmpView): the pending per-item runs behind the
-// index launch_lookup_index builds, or a dense device table -- or one uploaded
-// slice of a host-resident one -- cut into pieces by launch_compare_cut.  The
-// side with more entries drives the merge (okm_compare.hip), and the shared
-// sums are swapped back to (a, b) at the end.  Host-resident tables go up in
-// slices as the lookup's do; with both sides host-resident the slices nest:
-// the shared sums of disjoint key slices add, each side's totals are taken
-// once (a's with every slice of a, b's during a's first slice).  All scratch
-// comes from a's pool and runs on a's stream; b's stream is drained first.
-namespace {
-struct CmpSide {
-    okm_ctx *t;
-    bool pending = false, sliced = false;
-    uint64_t sl = 0, nslices = 0;  // entries per slice; an empty table has no slice
-    unsigned long long *pos = nullptr, *stmp = nullptr, *n_desc = nullptr;
-    uint64_t *first = nullptr, *tk = nullptr, *tc = nullptr;
-    LookItem *desc = nullptr;
-    CmpView v;
-    uint32_t T;  // the call's tile (compare_tile): a dense table is cut into pieces of it
-    CmpSide(okm_ctx *c, uint32_t tile) : t(c), T(tile) {
-        if (!c->n_res) return;
-        pending = c->pend.on;
-        sliced = !pending && c->res_host;
-        sl = c->n_res;
-        if (sliced) {
-            sl = uint64_t(1) << 26;
-            if (const int64_t e = test_knob(OKM_TEST_HIST_SLICE); e > 0) sl = (uint64_t)e;  // tests: several / ragged slices
-            sl = std::min(sl, c->n_res);
-        }
-        nslices = (c->n_res + sl - 1) / sl;
-        v.max_runs = pending ? c->pend.nitems : (uint32_t)((sl + T - 1) / T);
-        v.narrow = pending && c->pend.narrow;
-    }
-    uint64_t slice_len(uint64_t si) const { return std::min(sl, t->n_res - si * sl); }
-    double slice_bytes(uint64_t si) const { return (8.0 * t->kw + (v.narrow ? 4.0 : 8.0)) * (double)slice_len(si); }
-    okm_status prepare(Blocks &scratch) {
-        if (!nslices) return OKM_OK;
-        const uint64_t kw = t->kw, nr = v.max_runs;
-        if (pending) {
-            OKM_TRY(scratch.get((size_t)nr + 1, &pos));
-            OKM_TRY(scratch.get(scan_tmp_elems(nr + 1), &stmp));
-            n_desc = pos + nr;
-        } else {
-            OKM_TRY(scratch.get(1, &n_desc));
-        }
-        OKM_TRY(scratch.get((size_t)nr * kw, &first));
-        OKM_TRY(scratch.get((size_t)nr, &desc));
-        if (sliced) {
-            OKM_TRY(scratch.get(sl * kw, &tk));
-            OKM_TRY(scratch.get(sl, &tc));
-        }
-        v.first = first;
-        v.desc = desc;
-        v.n_desc = n_desc;
-        return OKM_OK;
-    }
-    okm_status upload(hipStream_t s, uint64_t si) {
-        if (!sliced) return OKM_OK;
-        const uint64_t o = si * sl, len = slice_len(si), kw = t->kw;
-        HIP_TRY(hipMemcpyAsync(tk, t->res_keys + o * kw, len * kw * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(tc, t->res_counts + o, len * 8, hipMemcpyHostToDevice, s));
-        return OKM_OK;
-    }
-    // slice si as a run list
-    void index(hipStream_t s, uint64_t si) {
-        v.n = slice_len(si);
-        if (pending) {
-            v.counts = t->pend.sc;
-            launch_lookup_index(s, t->pend.items, t->pend.nitems, t->pend.n_out, t->pend.sk, t->wide, pos, stmp, first,
-                                desc);
-        } else {
-            v.counts = sliced ? tc : t->res_counts;
-            launch_compare_cut(s, sliced ? tk : t->res_keys, v.n, t->wide, T, first, desc, n_desc);
-        }
-    }
-};
-}  // namespace
-
+// Two counted tables merged, each read as a run list (TableForm::Runs, cut at
+// the call's compare_tile).  The side with more entries drives the merge
+// (okm_compare.hip), and the shared sums are swapped back to (a, b) at the
+// end.  With both sides host-resident the slices nest: the shared sums of
+// disjoint key slices add, each side's totals are taken once (a's with every
+// slice of a, b's during a's first slice).  An empty side has no slice and
+// takes part in nothing.  All scratch comes from a's pool and runs on a's
+// stream; b's stream is drained first.
 okm_status okm_compare_counts(okm_ctx *a, okm_ctx *b, uint64_t min_count_a, uint64_t min_count_b,
                               okm_count_compare *out) {
     if (!a || !b || !out) return fail(OKM_E_ARG, "okm_compare_counts: null argument");
@@ -3736,21 +3720,23 @@ okm_status okm_compare_counts(okm_ctx *a, okm_ctx *b, uint64_t min_count_a, uint
     OKM_TRY(scratch.get(8, &acc));
     HIP_TRY(hipMemsetAsync(acc, 0, 8 * sizeof(unsigned long long), s));
     const uint32_t tile = compare_tile(a->wide);
-    CmpSide A(a, tile), B(b, tile);
+    TableReader A(a, TableForm::Runs, tile), B(b, TableForm::Runs, tile);
     OKM_TRY(A.prepare(scratch));
     OKM_TRY(B.prepare(scratch));
     const bool a_drives = a->n_res >= b->n_res;
-    CmpSide &D = a_drives ? A : B, &S = a_drives ? B : A;
+    const TableReader &D = a_drives ? A : B, &S = a_drives ? B : A;
     unsigned long long *toff = nullptr, *ttmp = nullptr, *slots = nullptr;
     CmpTile *tiles = nullptr;
     if (S.nslices) {  // (then D has entries too)
         OKM_TRY(scratch.get(compare_slot_words(), &slots));
         HIP_TRY(hipMemsetAsync(slots, 0, compare_slot_words() * sizeof(unsigned long long), s));
-        OKM_TRY(scratch.get((size_t)D.v.max_runs + 1, &toff));
-        OKM_TRY(scratch.get(scan_tmp_elems((uint64_t)D.v.max_runs + 1), &ttmp));
-        OKM_TRY(scratch.get(compare_max_tiles(D.sl, D.v.max_runs, tile), &tiles));
+        OKM_TRY(scratch.get((size_t)D.max_runs + 1, &toff));
+        OKM_TRY(scratch.get(scan_tmp_elems((uint64_t)D.max_runs + 1), &ttmp));
+        OKM_TRY(scratch.get(compare_max_tiles(D.sl, D.max_runs, tile), &tiles));
     }
     const bool has_a = A.nslices > 0, has_b = B.nslices > 0;
+    const auto view_bytes = [&](const TableView &v) { return (8.0 * a->kw + (v.narrow ? 4.0 : 8.0)) * (double)v.n; };
+    TableView va, vb;  // a's slice si, b's slice sj
     for (uint64_t si = 0; si < std::max<uint64_t>(A.nslices, 1); ++si) {
         for (uint64_t sj = 0; sj < std::max<uint64_t>(B.nslices, 1); ++sj) {
             const bool a_new = has_a && sj == 0;                          // a's slice si: index it, take its totals
@@ -3761,16 +3747,20 @@ okm_status okm_compare_counts(okm_ctx *a, okm_ctx *b, uint64_t min_count_a, uint
             double bytes = 0;  // the keys and counts of both tables, once each
             if (a_new) {
                 A.index(s, si);
-                launch_compare_totals(s, A.v, min_count_a, acc + 4);
-                bytes += A.slice_bytes(si);
+                va = A.view(si);
+                launch_compare_totals(s, va, min_count_a, acc + 4);
+                bytes += view_bytes(va);
             }
-            if (b_new) B.index(s, sj);
+            if (b_new) {
+                B.index(s, sj);
+                vb = B.view(sj);
+            }
             if (has_b && si == 0) {
-                launch_compare_totals(s, B.v, min_count_b, acc + 6);
-                bytes += B.slice_bytes(sj);
+                launch_compare_totals(s, vb, min_count_b, acc + 6);
+                bytes += view_bytes(vb);
             }
             if (has_a && has_b)
-                launch_compare(s, D.v, S.v, a->wide, a_drives ? min_count_a : min_count_b,
+                launch_compare(s, a_drives ? va : vb, a_drives ? vb : va, a->wide, a_drives ? min_count_a : min_count_b,
                                a_drives ? min_count_b : min_count_a, toff, ttmp, tiles, slots);
             if (slots && si + 1 == A.nslices && sj + 1 == B.nslices) launch_compare_fold(s, slots, acc);
             a->timer.end(s, "compare_counts", bytes);
@@ -3792,12 +3782,11 @@ okm_status okm_compare_counts(okm_ctx *a, okm_ctx *b, uint64_t min_count_a, uint
     return OKM_OK;
 }
 
-// Per-record depths of reads against the table in the representation it lies
-// in, as okm_lookup_counts searches it: the pending per-item runs behind a
-// first-key index built once per call, a dense device table, or a
-// host-resident one in slices.  One launch sequence per (slice, batch):
+// Per-record depths of reads against the table, searched as okm_lookup_counts
+// searches it (TableForm::Search).  One launch sequence per (slice, batch):
 //   [launch_lookup_index, the first time]  k_depth_sep_count  scan
 //   k_read_depths  [k_depth_fix, after the batch's last slice]
+// An empty table still takes one scan, which counts the windows.
 // A device batch keeps its rows in the caller's array across the slices.  Host
 // records go up in chunks of whole records (kDepthChunk bytes, at least one
 // record) through scratch sized for the largest chunk; with several slices
@@ -3809,69 +3798,24 @@ namespace {
 struct DepthCall {
     okm_ctx *c;
     Blocks scratch;
-    bool pending, sliced;
-    uint64_t sl, nslices;
-    unsigned long long *pos = nullptr, *stmp = nullptr, *tiles = nullptr;
-    uint64_t *first = nullptr, *tk = nullptr, *tc = nullptr;
-    LookItem *desc = nullptr;
-    bool indexed = false;
-    explicit DepthCall(okm_ctx *ctx) : c(ctx), scratch(*ctx->pool) {
-        pending = c->pend.on;
-        sliced = !pending && c->res_host && c->n_res;
-        sl = c->n_res;
-        if (sliced) {
-            sl = uint64_t(1) << 26;
-            if (const int64_t e = test_knob(OKM_TEST_HIST_SLICE); e > 0) sl = (uint64_t)e;  // tests: several / ragged slices
-            sl = std::min(sl, c->n_res);
-        }
-        nslices = c->n_res ? (c->n_res + sl - 1) / sl : 1;  // an empty table: one scan, for the windows
-    }
+    TableReader tab;
+    uint64_t nslices;  // scans per batch
+    unsigned long long *tiles = nullptr;
+    explicit DepthCall(okm_ctx *ctx)
+        : c(ctx), scratch(*ctx->pool), tab(ctx, TableForm::Search), nslices(std::max<uint64_t>(tab.nslices, 1)) {}
     // the table's side of the scratch, and the tile words of a batch of at most max_bytes
     okm_status prepare(uint64_t max_bytes) {
-        const uint64_t kw = c->kw;
-        if (pending) {
-            const uint32_t ni = c->pend.nitems;
-            OKM_TRY(scratch.get((size_t)ni + 1, &pos));
-            OKM_TRY(scratch.get(scan_tmp_elems((uint64_t)ni + 1), &stmp));
-            OKM_TRY(scratch.get((size_t)ni * kw, &first));
-            OKM_TRY(scratch.get((size_t)ni, &desc));
-        } else if (sliced) {
-            OKM_TRY(scratch.get(sl * kw, &tk));
-            OKM_TRY(scratch.get(sl, &tc));
-        }
+        OKM_TRY(tab.prepare(scratch));
         const uint64_t nt = depth_tiles(max_bytes);
         OKM_TRY(scratch.get(2 * nt + scan_tmp_elems(nt) + 1, &tiles));
-        return OKM_OK;
-    }
-    okm_status upload_slice(uint64_t si) {
-        if (!sliced) return OKM_OK;
-        const uint64_t o = si * sl, len = std::min(sl, c->n_res - o), kw = c->kw;
-        HIP_TRY(hipMemcpyAsync(tk, c->res_keys + o * kw, len * kw * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(tc, c->res_counts + o, len * 8, hipMemcpyHostToDevice, c->stream));
         return OKM_OK;
     }
     // slice si's scan of one device batch into rows (zeroed before its slice 0)
     okm_status scan(uint64_t si, const uint8_t *d_seq, uint64_t nb, uint64_t nrec, uint64_t min_count,
                     okm_read_depth *rows, bool fix) {
-        DepthTable t;
-        if (pending) {
-            t.items = true;
-            t.narrow = c->pend.narrow;
-            t.first = first;
-            t.desc = desc;
-            t.n_desc = pos + c->pend.nitems;
-            t.sc = c->pend.sc;
-        } else {
-            t.keys = sliced ? tk : c->res_keys;
-            t.counts = sliced ? tc : c->res_counts;
-            t.n = c->n_res ? std::min(sl, c->n_res - si * sl) : 0;
-        }
         c->timer.begin(c->stream);
-        if (pending && !indexed)
-            launch_lookup_index(c->stream, c->pend.items, c->pend.nitems, c->pend.n_out, c->pend.sk, c->wide, pos, stmp,
-                                first, desc);
-        indexed = true;
-        launch_read_depths(c->stream, d_seq, nb, nrec, c->k, c->wide, t, min_count, si == 0, tiles, rows);
+        tab.index(c->stream, si);
+        launch_read_depths(c->stream, d_seq, nb, nrec, c->k, c->wide, tab.view(si), min_count, si == 0, tiles, rows);
         if (fix) launch_read_depths_fix(c->stream, rows, nrec);
         // the read bytes in and the rows out, once per batch however many slices scan it
         c->timer.end(c->stream, "read_depths", si == 0 ? (double)nb + 48.0 * (double)nrec : 0.0);
@@ -3903,7 +3847,7 @@ okm_status okm_read_depths_device(okm_ctx *c, const uint8_t *d_seq, uint64_t n_b
     }
     HIP_TRY(hipMemsetAsync(d_out, 0, n_records * sizeof(okm_read_depth), c->stream));
     for (uint64_t si = 0; n_bytes && si < d.nslices; ++si) {
-        OKM_TRY(d.upload_slice(si));
+        OKM_TRY(d.tab.upload(c->stream, si));
         OKM_TRY(d.scan(si, src, n_bytes, n_records, min_count, d_out, si + 1 == d.nslices));
     }
     OKM_TRY(sync(c));
@@ -3944,7 +3888,7 @@ okm_status okm_read_depths(okm_ctx *c, const uint8_t *seq, const uint64_t *offse
     std::vector<uint8_t> packed(max_bytes);
     std::vector<okm_read_depth> part(d.nslices > 1 ? max_recs : 0);
     for (uint64_t si = 0; si < d.nslices; ++si) {
-        OKM_TRY(d.upload_slice(si));
+        OKM_TRY(d.tab.upload(c->stream, si));
         for (const auto &ch : chunks) {
             const uint64_t r0 = ch.first, nr = ch.second - ch.first;
             const uint64_t nb = pack_records(packed.data(), seq, offsets, r0, ch.second, normalized);

@@ -325,45 +325,50 @@ void launch_hist_items(void *stream, const DevItem *items, uint32_t nitems, cons
 void launch_hist_dense(void *stream, const uint64_t *counts, uint64_t n, uint64_t n_bins, unsigned long long *hist,
                        unsigned long long *summary);
 
-// Count lookup (okm_lookup.hip): out[i] = the count of query i in a sorted
-// table, *found += queries present.  wide: keys and queries are K128 (two u64
-// each; pointers stay uint64_t*, lengths count keys).
-// The pending segmented table is searched in two levels.  launch_lookup_index
-// builds the first: the first key of every item that owns one (not kItemEmpty,
-// n_out > 0), in item order, and a descriptor of its run.  Scratch: pos =
-// nitems + 1 words (pos[nitems] = items kept, read on the device), scan_tmp =
-// scan_tmp_elems(nitems + 1), first = nitems keys, desc = nitems LookItem.
+// A counted table as the in-place readers' kernels see it (the lookup, the
+// depth, the compare): one of two forms, both sorted by key.  The host's
+// TableReader (okm_engine.hip) fills it for the representation the table lies
+// in.  wide: keys are K128 (two u64 each; pointers stay uint64_t*, lengths
+// count keys).
+// The run list is the pending segmented table behind launch_lookup_index's
+// index: the first key of every item that owns one (not kItemEmpty, n_out >
+// 0), in item order, and a descriptor of its run.  launch_compare_cut writes
+// the same arrays for a flat table.
 struct LookItem {
     const uint64_t *keys;  // the run's ascending keys
     uint64_t coff;         // its counts start at counts[coff] (u32 or u64 words)
     uint64_t n;            // entries, > 0
 };
-void launch_lookup_index(void *stream, const DevItem *items, uint32_t nitems, const unsigned long long *n_out,
-                         const uint64_t *src_keys, bool wide, unsigned long long *pos, unsigned long long *scan_tmp,
-                         uint64_t *first, LookItem *desc);
-void launch_lookup_items(void *stream, const uint64_t *first, const LookItem *desc, const unsigned long long *n_desc,
-                         const uint64_t *src_counts, bool narrow, bool wide, const uint64_t *queries, uint64_t nq,
-                         uint64_t *out, unsigned long long *found);
-// A dense table keys[n] / counts[n].  hits_only: absent queries leave out[i]
-// as it is (one slice of a host-resident table; out zeroed by the caller).
-void launch_lookup_dense(void *stream, const uint64_t *keys, const uint64_t *counts, uint64_t n, bool wide,
-                         const uint64_t *queries, uint64_t nq, uint64_t *out, unsigned long long *found,
-                         bool hits_only);
-
-// Count compare (okm_compare.hip): two counted tables merged where they lie.
-// Every representation is read through a run list, as launch_lookup_index
-// builds it for a pending table; launch_compare_cut writes the same arrays for
-// a dense table keys[n] (pieces of `tile` entries, the call's compare_tile: first and desc
-// hold ceil(n / tile) entries, *n_desc receives that number).
-struct CmpView {
+struct TableView {
+    bool runs = false;                            // the run list below is filled: read the table through it
+    uint64_t n = 0;                               // entries (0: an empty table, nothing is read)
+    const uint64_t *keys = nullptr;               // flat: keys[n], a dense table or one uploaded slice
+    const uint64_t *counts = nullptr;             // flat: counts[n]; run r's at counts[desc[r].coff] (u32 when narrow)
     const uint64_t *first = nullptr;              // the first key of every run
     const LookItem *desc = nullptr;
     const unsigned long long *n_desc = nullptr;   // device: runs
-    const uint64_t *counts = nullptr;             // run r's counts at counts[desc[r].coff] (u32 words when narrow)
-    bool narrow = false;
     uint32_t max_runs = 0;                        // the host's bound of *n_desc
-    uint64_t n = 0;                               // entries
+    bool narrow = false;
 };
+
+// Count lookup (okm_lookup.hip): out[i] = the count of query i in the table,
+// *found += queries present.
+// launch_lookup_index builds a pending table's run list.  Scratch: pos =
+// nitems + 1 words (pos[nitems] = items kept, read on the device), scan_tmp =
+// scan_tmp_elems(nitems + 1), first = nitems keys, desc = nitems LookItem.
+void launch_lookup_index(void *stream, const DevItem *items, uint32_t nitems, const unsigned long long *n_out,
+                         const uint64_t *src_keys, bool wide, unsigned long long *pos, unsigned long long *scan_tmp,
+                         uint64_t *first, LookItem *desc);
+// hits_only (a flat view only): absent queries leave out[i] as it is (one
+// slice of a host-resident table; out zeroed by the caller).
+void launch_lookup(void *stream, const TableView &t, bool wide, const uint64_t *queries, uint64_t nq, uint64_t *out,
+                   unsigned long long *found, bool hits_only);
+
+// Count compare (okm_compare.hip): two counted tables merged where they lie.
+// Every representation is read through a TableView's run list;
+// launch_compare_cut writes one for a flat table keys[n] (pieces of `tile`
+// entries, the call's compare_tile: first and desc hold ceil(n / tile)
+// entries, *n_desc receives that number).
 // One tile of the driving table and the range of the other table under its key span (k_cmp_bounds).
 struct CmpTile {
     uint32_t d_run, d_len;
@@ -376,7 +381,7 @@ uint64_t compare_max_tiles(uint64_t n, uint32_t max_runs, uint32_t tile);
 void launch_compare_cut(void *stream, const uint64_t *keys, uint64_t n, bool wide, uint32_t tile, uint64_t *first,
                         LookItem *desc, unsigned long long *n_desc);
 // out[0] += entries of v with count >= min_count, out[1] += the sum of their counts (mod 2^64).
-void launch_compare_totals(void *stream, const CmpView &v, uint64_t min_count, unsigned long long *out);
+void launch_compare_totals(void *stream, const TableView &v, uint64_t min_count, unsigned long long *out);
 // Over the keys in both d and s whose counts pass min_d / min_s: their
 // number, sum of min(count_d, count_s), sum of count_d, sum of count_s, added
 // into words 0..3 of one of the slots of out (compare_slot_words() words,
@@ -384,7 +389,7 @@ void launch_compare_totals(void *stream, const CmpView &v, uint64_t min_count, u
 // launch_compare_fold then adds the slots' sums to out4[0..3].  d drives (the larger table).  Scratch:
 // toff = d.max_runs + 1 words, scan_tmp = scan_tmp_elems(d.max_runs + 1),
 // tiles = compare_max_tiles(d.n, d.max_runs, compare_tile(wide)).
-void launch_compare(void *stream, const CmpView &d, const CmpView &s, bool wide, uint64_t min_d, uint64_t min_s,
+void launch_compare(void *stream, const TableView &d, const TableView &s, bool wide, uint64_t min_d, uint64_t min_s,
                     unsigned long long *toff, unsigned long long *scan_tmp, CmpTile *tiles, unsigned long long *out);
 size_t compare_slot_words();
 void launch_compare_fold(void *stream, const unsigned long long *slots, unsigned long long *out4);
@@ -392,26 +397,16 @@ void launch_compare_fold(void *stream, const unsigned long long *slots, unsigned
 // Per-record k-mer depth (okm_depth.hip): one scan of a device batch (records
 // joined by separators, 16-byte aligned, n bytes) against one representation
 // of the table; rows[r] accumulates record r's okm_read_depth (r = separators
-// before the window, rows past nrec dropped).  The table is either dense
-// (keys / counts / n; n == 0: empty) or the pending runs behind
-// launch_lookup_index's index (items: first / desc / n_desc / sc / narrow).
+// before the window, rows past nrec dropped).  The table is searched as the
+// lookup searches it, flat or through a pending table's run list.
 // Rows start zeroed; any number of launches (slices of a host-resident table)
 // add into them, exactly one of them with count_windows; the min field holds
 // the largest ~count until launch_read_depths_fix turns it round, once, after
 // the last launch.  tiles: 2 * depth_tiles(n) + scan_tmp_elems(depth_tiles(n))
 // words of scratch; depth_tiles(n) < 2^31.
-struct DepthTable {
-    const uint64_t *keys = nullptr, *counts = nullptr;
-    uint64_t n = 0;
-    bool items = false, narrow = false;
-    const uint64_t *first = nullptr;
-    const LookItem *desc = nullptr;
-    const unsigned long long *n_desc = nullptr;
-    const uint64_t *sc = nullptr;
-};
 uint64_t depth_tiles(uint64_t n_bytes);
 void launch_read_depths(void *stream, const uint8_t *seq, uint64_t n, uint64_t nrec, uint32_t k, bool wide,
-                        const DepthTable &t, uint64_t min_count, bool count_windows, unsigned long long *tiles,
+                        const TableView &t, uint64_t min_count, bool count_windows, unsigned long long *tiles,
                         okm_read_depth *rows);
 void launch_read_depths_fix(void *stream, okm_read_depth *rows, uint64_t nrec);
 // a += b for rows taken over the same reads against tables of disjoint keys

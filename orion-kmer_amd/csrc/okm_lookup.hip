@@ -48,38 +48,41 @@ __device__ __forceinline__ void look_found(uint32_t mine, ull *__restrict__ foun
     }
 }
 
+// The two lookup kernels: load the queries, find them (okm_search.h), store.
+// HITS_ONLY is a property of the store: one slice of several writes only what
+// it finds.
+template <typename KT, typename TAB, bool HITS_ONLY>
+__device__ __forceinline__ void look_queries(TAB tab, const ull *__restrict__ queries, ull nq, ull *__restrict__ out,
+                                             ull *__restrict__ found) {
+    typedef KeyOps<KT> O;
+    const ull base = (ull)blockIdx.x * (kLookBlock * kLookFly) + threadIdx.x;
+    KT q[kLookFly];
+    bool live[kLookFly], hit[kLookFly];
+    ull c[kLookFly];
+    tab.begin();
+#pragma unroll
+    for (int f = 0; f < kLookFly; ++f) {
+        const ull i = base + (ull)f * kLookBlock;
+        live[f] = i < nq;
+        q[f] = live[f] ? load_query<KT>(queries, i) : O::empty();
+    }
+    tab.find(q, live, c, hit);
+    uint32_t hits = 0;
+#pragma unroll
+    for (int f = 0; f < kLookFly; ++f) {
+        const ull i = base + (ull)f * kLookBlock;
+        hits += hit[f] ? 1u : 0u;
+        if (live[f] && (!HITS_ONLY || c[f])) out[i] = c[f];  // (a table entry's count is never 0)
+    }
+    look_found(hits, found);
+}
+
 template <typename KT, bool HITS_ONLY>
 __global__ __launch_bounds__(kLookBlock) void k_lookup_dense(const KT *__restrict__ keys,
                                                              const uint64_t *__restrict__ counts, ull n,
                                                              const ull *__restrict__ queries, ull nq,
                                                              ull *__restrict__ out, ull *__restrict__ found) {
-    typedef KeyOps<KT> O;
-    const ull base = (ull)blockIdx.x * (kLookBlock * kLookFly) + threadIdx.x;
-    FlatKeys<KT> a[kLookFly];
-    ull len[kLookFly], pos[kLookFly];
-    KT q[kLookFly], last[kLookFly];
-#pragma unroll
-    for (int f = 0; f < kLookFly; ++f) {
-        const ull i = base + (ull)f * kLookBlock;
-        a[f].p = keys;
-        len[f] = i < nq ? n : 0;
-        q[f] = i < nq ? load_query<KT>(queries, i) : O::empty();
-    }
-    search_last_le<KT, kLookFly>(a, len, q, pos, last);
-    uint32_t hits = 0;
-    ull c[kLookFly];
-#pragma unroll
-    for (int f = 0; f < kLookFly; ++f) {
-        const bool hit = len[f] && O::eq(last[f], q[f]);
-        c[f] = hit ? counts[pos[f]] : 0;
-        hits += hit ? 1u : 0u;
-    }
-#pragma unroll
-    for (int f = 0; f < kLookFly; ++f) {
-        const ull i = base + (ull)f * kLookBlock;
-        if (i < nq && (!HITS_ONLY || c[f])) out[i] = c[f];  // (a table entry's count is never 0)
-    }
-    look_found(hits, found);
+    look_queries<KT, FindDense<KT, kLookFly>, HITS_ONLY>({keys, counts, n}, queries, nq, out, found);
 }
 
 template <typename KT, bool NARROW>
@@ -89,49 +92,7 @@ __global__ __launch_bounds__(kLookBlock) void k_lookup_items(const KT *__restric
                                                              const uint64_t *__restrict__ sc,
                                                              const ull *__restrict__ queries, ull nq,
                                                              ull *__restrict__ out, ull *__restrict__ found) {
-    typedef KeyOps<KT> O;
-    const ull m = *n_desc;
-    const ull base = (ull)blockIdx.x * (kLookBlock * kLookFly) + threadIdx.x;
-    FlatKeys<KT> a[kLookFly];
-    ull len[kLookFly], pos[kLookFly], coff[kLookFly];
-    KT q[kLookFly], last[kLookFly];
-#pragma unroll
-    for (int f = 0; f < kLookFly; ++f) {
-        const ull i = base + (ull)f * kLookBlock;
-        a[f].p = first;
-        len[f] = i < nq ? m : 0;
-        q[f] = i < nq ? load_query<KT>(queries, i) : O::empty();
-    }
-    // the item whose first key is the last one <= the query: no other item's range can hold it
-    search_last_le<KT, kLookFly>(a, len, q, pos, last);
-#pragma unroll
-    for (int f = 0; f < kLookFly; ++f) {
-        const bool owned = len[f] && !O::lt(q[f], last[f]);  // else: below the table's first key
-        len[f] = 0;
-        coff[f] = 0;
-        if (owned) {
-            const LookItem *d = desc + pos[f];
-            a[f].p = reinterpret_cast<const KT *>(gload(&d->keys));
-            coff[f] = gload(&d->coff);
-            len[f] = gload(&d->n);
-        }
-    }
-    search_last_le<KT, kLookFly>(a, len, q, pos, last);
-    const uint32_t *sc32 = reinterpret_cast<const uint32_t *>(sc);
-    uint32_t hits = 0;
-    ull c[kLookFly];
-#pragma unroll
-    for (int f = 0; f < kLookFly; ++f) {
-        const bool hit = len[f] && O::eq(last[f], q[f]);
-        c[f] = !hit ? 0 : NARROW ? (ull)sc32[coff[f] + pos[f]] : (ull)sc[coff[f] + pos[f]];
-        hits += hit ? 1u : 0u;
-    }
-#pragma unroll
-    for (int f = 0; f < kLookFly; ++f) {
-        const ull i = base + (ull)f * kLookBlock;
-        if (i < nq) out[i] = c[f];
-    }
-    look_found(hits, found);
+    look_queries<KT, FindItems<KT, NARROW, kLookFly>, false>({first, desc, n_desc, sc, 0}, queries, nq, out, found);
 }
 
 // flags[i] = item i owns a key, i < nitems; flags[nitems] = 0 (the scan's total lands there)
@@ -183,44 +144,37 @@ static dim3 look_grid(uint64_t nq) {
     return dim3((uint32_t)((nq + kLookBlock * kLookFly - 1) / (kLookBlock * kLookFly)));
 }
 
-void launch_lookup_items(void *stream, const uint64_t *first, const LookItem *desc, const unsigned long long *n_desc,
-                         const uint64_t *src_counts, bool narrow, bool wide, const uint64_t *queries, uint64_t nq,
-                         uint64_t *out, unsigned long long *found) {
+void launch_lookup(void *stream, const TableView &t, bool wide, const uint64_t *queries, uint64_t nq, uint64_t *out,
+                   unsigned long long *found, bool hits_only) {
     if (!nq) return;
     hipStream_t s = (hipStream_t)stream;
     const dim3 g = look_grid(nq), b(kLookBlock);
-    const K128 *f2 = reinterpret_cast<const K128 *>(first);
-    const ull *f1 = reinterpret_cast<const ull *>(first);
     const ull *q = reinterpret_cast<const ull *>(queries);
     ull *o = reinterpret_cast<ull *>(out);
-    if (wide && narrow)
-        hipLaunchKernelGGL((k_lookup_items<K128, true>), g, b, 0, s, f2, desc, n_desc, src_counts, q, nq, o, found);
-    else if (wide)
-        hipLaunchKernelGGL((k_lookup_items<K128, false>), g, b, 0, s, f2, desc, n_desc, src_counts, q, nq, o, found);
-    else if (narrow)
-        hipLaunchKernelGGL((k_lookup_items<ull, true>), g, b, 0, s, f1, desc, n_desc, src_counts, q, nq, o, found);
-    else
-        hipLaunchKernelGGL((k_lookup_items<ull, false>), g, b, 0, s, f1, desc, n_desc, src_counts, q, nq, o, found);
-}
-
-void launch_lookup_dense(void *stream, const uint64_t *keys, const uint64_t *counts, uint64_t n, bool wide,
-                         const uint64_t *queries, uint64_t nq, uint64_t *out, unsigned long long *found,
-                         bool hits_only) {
-    if (!nq) return;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 g = look_grid(nq), b(kLookBlock);
-    const K128 *k2 = reinterpret_cast<const K128 *>(keys);
-    const ull *k1 = reinterpret_cast<const ull *>(keys);
-    const ull *q = reinterpret_cast<const ull *>(queries);
-    ull *o = reinterpret_cast<ull *>(out);
+    if (t.runs) {
+        const K128 *f2 = reinterpret_cast<const K128 *>(t.first);
+        const ull *f1 = reinterpret_cast<const ull *>(t.first), *nd = t.n_desc;
+        const uint64_t *sc = t.counts;
+        if (wide && t.narrow)
+            hipLaunchKernelGGL((k_lookup_items<K128, true>), g, b, 0, s, f2, t.desc, nd, sc, q, nq, o, found);
+        else if (wide)
+            hipLaunchKernelGGL((k_lookup_items<K128, false>), g, b, 0, s, f2, t.desc, nd, sc, q, nq, o, found);
+        else if (t.narrow)
+            hipLaunchKernelGGL((k_lookup_items<ull, true>), g, b, 0, s, f1, t.desc, nd, sc, q, nq, o, found);
+        else
+            hipLaunchKernelGGL((k_lookup_items<ull, false>), g, b, 0, s, f1, t.desc, nd, sc, q, nq, o, found);
+        return;
+    }
+    const K128 *k2 = reinterpret_cast<const K128 *>(t.keys);
+    const ull *k1 = reinterpret_cast<const ull *>(t.keys);
     if (wide && hits_only)
-        hipLaunchKernelGGL((k_lookup_dense<K128, true>), g, b, 0, s, k2, counts, n, q, nq, o, found);
+        hipLaunchKernelGGL((k_lookup_dense<K128, true>), g, b, 0, s, k2, t.counts, t.n, q, nq, o, found);
     else if (wide)
-        hipLaunchKernelGGL((k_lookup_dense<K128, false>), g, b, 0, s, k2, counts, n, q, nq, o, found);
+        hipLaunchKernelGGL((k_lookup_dense<K128, false>), g, b, 0, s, k2, t.counts, t.n, q, nq, o, found);
     else if (hits_only)
-        hipLaunchKernelGGL((k_lookup_dense<ull, true>), g, b, 0, s, k1, counts, n, q, nq, o, found);
+        hipLaunchKernelGGL((k_lookup_dense<ull, true>), g, b, 0, s, k1, t.counts, t.n, q, nq, o, found);
     else
-        hipLaunchKernelGGL((k_lookup_dense<ull, false>), g, b, 0, s, k1, counts, n, q, nq, o, found);
+        hipLaunchKernelGGL((k_lookup_dense<ull, false>), g, b, 0, s, k1, t.counts, t.n, q, nq, o, found);
 }
 
 }  // namespace okm

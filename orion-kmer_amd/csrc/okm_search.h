@@ -1,12 +1,15 @@
 // okm_search.h — the search every in-place reader of a counted table shares
-// (okm_lookup.hip, okm_depth.hip).
+// (okm_lookup.hip, okm_depth.hip, okm_compare.hip), and the two finders built
+// on it: FindDense and FindItems, one per form of a TableView
+// (okm_internal.h), used by the lookup and the depth kernels.
 //
 // Every representation of the table is sorted by key, so a lookup is a search,
 // and all of them use one routine, search_last_le: the position of the last
 // key <= the query in a sorted range read through an accessor.  Its step count
 // depends on the range's length only, never on the data, so a lane can keep
 // several queries in flight (QF) that issue their loads together, level by
-// level.
+// level.  (The compare's k_cmp_bounds searches for ranges, not for hits, and
+// calls search_last_le itself.)
 #pragma once
 
 #include "okm_dev_common.h"
@@ -72,5 +75,83 @@ template <>
 __device__ __forceinline__ K128 load_query<K128>(const ull *queries, ull i) {
     return K128{queries[2 * i], queries[2 * i + 1]};
 }
+
+// The table's two forms: find() answers QF queries at once (live[f]: query f
+// is one), hit[f] and, where hit, its count (else 0).  begin() runs once per
+// thread before the first find().
+
+// keys[n] / counts[n], a dense table or one uploaded slice (n == 0: an empty
+// table, nothing is read)
+template <typename KT, int QF>
+struct FindDense {
+    const KT *keys;
+    const uint64_t *counts;
+    ull n;
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ void find(const KT (&q)[QF], const bool (&live)[QF], ull (&cnt)[QF],
+                                         bool (&hit)[QF]) const {
+        typedef KeyOps<KT> O;
+        FlatKeys<KT> a[QF];
+        ull len[QF], pos[QF];
+        KT last[QF];
+#pragma unroll
+        for (int f = 0; f < QF; ++f) {
+            a[f].p = keys;
+            len[f] = live[f] ? n : 0;
+        }
+        search_last_le<KT, QF>(a, len, q, pos, last);
+#pragma unroll
+        for (int f = 0; f < QF; ++f) {
+            hit[f] = len[f] && O::eq(last[f], q[f]);
+            cnt[f] = hit[f] ? counts[pos[f]] : 0;
+        }
+    }
+};
+
+// The pending per-item runs behind launch_lookup_index's first-key index, two
+// levels: the item whose range holds the query, then that item's run, whose
+// count lies at the same position; NARROW: the runs' counts are u32.
+template <typename KT, bool NARROW, int QF>
+struct FindItems {
+    const KT *first;
+    const LookItem *desc;
+    const ull *n_desc;
+    const uint64_t *sc;
+    ull m;
+    __device__ __forceinline__ void begin() { m = *n_desc; }
+    __device__ __forceinline__ void find(const KT (&q)[QF], const bool (&live)[QF], ull (&cnt)[QF],
+                                         bool (&hit)[QF]) const {
+        typedef KeyOps<KT> O;
+        FlatKeys<KT> a[QF];
+        ull len[QF], pos[QF], coff[QF];
+        KT last[QF];
+#pragma unroll
+        for (int f = 0; f < QF; ++f) {
+            a[f].p = first;
+            len[f] = live[f] ? m : 0;
+        }
+        // the item whose first key is the last one <= the query: no other item's range can hold it
+        search_last_le<KT, QF>(a, len, q, pos, last);
+#pragma unroll
+        for (int f = 0; f < QF; ++f) {
+            const bool owned = len[f] && !O::lt(q[f], last[f]);  // else: below the table's first key
+            len[f] = 0;
+            coff[f] = 0;
+            if (owned) {
+                const LookItem *d = desc + pos[f];
+                a[f].p = reinterpret_cast<const KT *>(gload(&d->keys));
+                coff[f] = gload(&d->coff);
+                len[f] = gload(&d->n);
+            }
+        }
+        search_last_le<KT, QF>(a, len, q, pos, last);
+        const uint32_t *sc32 = reinterpret_cast<const uint32_t *>(sc);
+#pragma unroll
+        for (int f = 0; f < QF; ++f) {
+            hit[f] = len[f] && O::eq(last[f], q[f]);
+            cnt[f] = !hit[f] ? 0 : NARROW ? (ull)sc32[coff[f] + pos[f]] : (ull)sc[coff[f] + pos[f]];
+        }
+    }
+};
 
 }  // namespace okm
