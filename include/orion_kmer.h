@@ -265,6 +265,37 @@ typedef struct okm_count_compare {
 okm_status okm_compare_counts(okm_ctx *a, okm_ctx *b, uint64_t min_count_a, uint64_t min_count_b,
                               okm_count_compare *out);
 
+/* Two counted tables combined into a third -- `kmc_tools simple` union /
+ * intersect / kmers_subtract / counters_subtract, meryl union-sum / intersect /
+ * difference / subtract; an extension.  "Kept" means what it means for
+ * okm_compare_counts: an entry whose count is at least its side's min_count
+ * (0 behaves as 1); an entry that is not kept is treated as absent from its
+ * side.  The union's sum saturates at 2^64 - 1, and no output entry has count
+ * 0.  Both inputs are counted first if batches are pending, and are read-only:
+ * a count's per-item runs are merged in place (narrow u32 counts included), a
+ * dense table where it lies.  A host-resident input is first moved to the
+ * device; if it does not fit the call fails with OKM_E_NOMEM (an output of
+ * that size would not fit either).  `out` is reset first and then holds the
+ * result as a dense, sorted, counted device table that stands for its input:
+ * every reader works on it, and later okm_add_* calls add to it.  *n_out (may
+ * be NULL) receives its entries; an empty result leaves `out` an empty counted
+ * context.  The output is allocated at its exact size from out's pool and has
+ * no host tier: if it cannot be had the call returns OKM_E_NOMEM, `out` is
+ * left reset and a and b stay as they were.  a == b is allowed.  out == a,
+ * out == b, a null context or an unknown op: OKM_E_ARG.  Any set-mode context:
+ * OKM_E_STATE.  Contexts (out included) of different k, width or device:
+ * OKM_E_ARG. */
+typedef enum okm_combine_op {
+    OKM_COMBINE_UNION = 0,         /* keys kept in a or b;   count = count_a + count_b (an absent side adds 0) */
+    OKM_COMBINE_INTERSECT_MIN = 1, /* keys kept in a and b;  count = min(count_a, count_b) */
+    OKM_COMBINE_INTERSECT_A = 2,   /* keys kept in a and b;  count = count_a */
+    OKM_COMBINE_DIFFERENCE = 3,    /* keys kept in a, not kept in b; count = count_a   (kmc kmers_subtract, meryl difference) */
+    OKM_COMBINE_SUBTRACT = 4       /* keys kept in a; count = count_a - count_b where b keeps the key;
+                                      entries whose result is <= 0 are dropped (kmc counters_subtract, meryl subtract) */
+} okm_combine_op;
+okm_status okm_combine_counts(okm_ctx *a, okm_ctx *b, okm_combine_op op, uint64_t min_count_a, uint64_t min_count_b,
+                              okm_ctx *out, uint64_t *n_out /* may be NULL */);
+
 /* Device pointers to the counted, sorted, unfiltered table (valid until the
  * next add/reset/destroy). */
 okm_status okm_result_device(okm_ctx *ctx, const uint64_t **d_keys, const uint64_t **d_counts,

@@ -219,7 +219,7 @@ static const char *kVersion = "orion-kmer 0.1.0";
 
 static void print_help(const std::string &cmd) {
     if (cmd == "count")
-        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n      --depth <FASTX>              Take the k-mer depth of every record of FASTX in the whole table (extension)\n      --depth-output <FILE>        Where --depth writes id<TAB>windows<TAB>present<TAB>solid<TAB>sum<TAB>min<TAB>max, in input order\n      --depth-min-count <N>        A window is solid when its k-mer's count is at least N [default: 2]\n      --compare <FASTX>            Count FASTX as a second table (same k) and compare the two tables with their counts (extension)\n      --compare-output <FILE>      Where --compare writes field<TAB>value: the shared k-mers, their counts, Jaccard, weighted Jaccard, Bray-Curtis\n      --compare-min-count <N>      Minimum count of a k-mer of the --compare table (--min-count: of the first table) [default: 1]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
+        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n      --depth <FASTX>              Take the k-mer depth of every record of FASTX in the whole table (extension)\n      --depth-output <FILE>        Where --depth writes id<TAB>windows<TAB>present<TAB>solid<TAB>sum<TAB>min<TAB>max, in input order\n      --depth-min-count <N>        A window is solid when its k-mer's count is at least N [default: 2]\n      --compare <FASTX>            Count FASTX as a second table (same k) and compare the two tables with their counts (extension)\n      --compare-output <FILE>      Where --compare writes field<TAB>value: the shared k-mers, their counts, Jaccard, weighted Jaccard, Bray-Curtis\n      --compare-min-count <N>      Minimum count of a k-mer of the --compare table (--min-count: of the first table) [default: 1]\n      --combine <FASTX>            Count FASTX as a second table (same k) and combine the two tables into a third (extension)\n      --combine-op <OP>            union, intersect, intersect_left, difference or subtract (the first table is the left one)\n      --combine-output <FILE>      Where --combine writes the combined table as KMER<TAB>COUNT lines\n      --combine-min-count <N>      Minimum count of a k-mer of the --combine table (--min-count: of the first table) [default: 1]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
     else if (cmd == "build")
         printf("Build a unique k-mer database from genome assemblies\n\nUsage: orion-kmer build [OPTIONS] --kmer-size <KMER_SIZE> --genomes <GENOME_FILES>... --output-file <OUTPUT_FILE>\n");
     else if (cmd == "compare")
@@ -477,6 +477,29 @@ static int write_compare(okm_ctx *first, uint8_t k, bool wide, const std::string
     return 0;
 }
 
+// --combine: the second input counted into a context of its own, the two
+// tables merged into a third context (okm_combine_counts; the first table is
+// a), and the third table written as the count's own KMER<TAB>COUNT lines.
+static const char *const kCombineOps[] = {"union", "intersect", "intersect_left", "difference", "subtract"};
+
+static int write_combine(okm_ctx *first, uint8_t k, bool wide, const std::string &path, int op,
+                         const std::string &out_path, uint64_t min_a, uint64_t min_b) {
+    CompareCtx second, third;
+    const okm_mode mode = (okm_mode)(OKM_MODE_COUNT | (wide ? OKM_MODE_WIDE : 0));
+    int rc = open_engine(&second.c, k, mode);
+    if (rc || (rc = open_engine(&third.c, k, mode))) return rc;
+    if ((rc = feed_file(second.c, path, true, "Failed to get input reader for combine file: "))) return rc;
+    uint64_t n = 0, got = 0;
+    if (!first || okm_combine_counts(first, second.c, (okm_combine_op)op, min_a, min_b, third.c, &n) != OKM_OK)
+        return die("GPU engine failure while combining the tables: " + err_detail());
+    std::vector<uint64_t> keys(n * (wide ? 2 : 1)), counts(n);
+    if (okm_fetch_counts(third.c, 1, keys.data(), counts.data(), n, &got, 0) != OKM_OK || got != n)
+        return die("GPU engine failure while fetching the combined table: " + err_detail());
+    if (okm_write_counts_tsv(out_path.c_str(), k, keys.data(), counts.data(), n) != OKM_OK)
+        return die("Failed to get output writer for combine output file: " + dbg_path(out_path));
+    return 0;
+}
+
 // count.rs:40-141
 static int run_count(const Args &a) {
     uint8_t k;
@@ -532,6 +555,32 @@ static int run_count(const Args &a) {
         return usage_error("invalid value '" + cm + "' for '--compare-min-count <N>'");
     if (want_cmp && g_gpus != 1)
         return usage_error("the argument '--compare <FASTX>' cannot be used with '--gpus <GPUS>' other than 1");
+    // --combine <FASTX> --combine-op <OP> --combine-output <FILE>
+    // [--combine-min-count <N>]: FASTX is counted at the same k into a second
+    // table and the two are combined into a third, written as KMER<TAB>COUNT
+    // (kmc_tools simple / meryl set operations; an extension); the first
+    // table is the left one, kept at --min-count, the second is kept at
+    // --combine-min-count; the three flags need one another.  One GPU only.
+    std::string cmb_path, cmb_op, cmb_out, cbm;
+    const bool want_cmb = get_one(a, "combine", cmb_path);
+    const bool has_cop = get_one(a, "combine-op", cmb_op), has_cout = get_one(a, "combine-output", cmb_out);
+    uint64_t cmb_min = 1;
+    const bool has_cmin = get_one(a, "combine-min-count", cbm);
+    if ((has_cop || has_cout || has_cmin) && !want_cmb)
+        return usage_error("the following required arguments were not provided:\n  --combine <FASTX>");
+    if (want_cmb && !(has_cop && has_cout))
+        return usage_error(std::string("the following required arguments were not provided:\n  ") +
+                           (has_cop ? "--combine-output <FILE>" : "--combine-op <OP>"));
+    int cmb_opi = -1;
+    for (int i = 0; i < 5; ++i)
+        if (cmb_op == kCombineOps[i]) cmb_opi = i;
+    if (want_cmb && cmb_opi < 0)
+        return usage_error("invalid value '" + cmb_op + "' for '--combine-op <OP>'\n  [possible values: union, "
+                           "intersect, intersect_left, difference, subtract]");
+    if (has_cmin && !parse_u64(cbm, cmb_min))
+        return usage_error("invalid value '" + cbm + "' for '--combine-min-count <N>'");
+    if (want_cmb && g_gpus != 1)
+        return usage_error("the argument '--combine <FASTX>' cannot be used with '--gpus <GPUS>' other than 1");
     // --wide: opt-in two-u64 keys for k in 33..64 (not in the reference, whose
     // error for k > 32 is kept byte-identical without it)
     std::string wflag;
@@ -606,6 +655,12 @@ static int run_count(const Args &a) {
         if ((rc = write_compare(okm_group_owner(grp, 0), k, wide, cmp_path, cmp_out, min_count, cmp_min))) return rc;
         info("orion_kmer::commands::count", "Successfully wrote the table comparison to " + dbg_path(cmp_out));
         phase("compare");
+    }
+    if (want_cmb) {  // both tables are merged as their counts left them, into a table of its own
+        if ((rc = write_combine(okm_group_owner(grp, 0), k, wide, cmb_path, cmb_opi, cmb_out, min_count, cmb_min)))
+            return rc;
+        info("orion_kmer::commands::count", "Successfully wrote the combined table to " + dbg_path(cmb_out));
+        phase("combine");
     }
     okm_status s = okm_group_write_counts_tsv(grp, out.c_str(), min_count, nullptr);
     phase("written");
@@ -1162,6 +1217,10 @@ int main(int argc, char **argv) {
         spec.push_back({"compare", 0, true, false});
         spec.push_back({"compare-output", 0, true, false});
         spec.push_back({"compare-min-count", 0, true, false});
+        spec.push_back({"combine", 0, true, false});
+        spec.push_back({"combine-op", 0, true, false});
+        spec.push_back({"combine-output", 0, true, false});
+        spec.push_back({"combine-min-count", 0, true, false});
     } else if (cmd == "build") {
         spec.push_back({"kmer-size", 'k', true, false});
         spec.push_back({"genomes", 'g', true, true});

@@ -47,13 +47,13 @@
 // a few thousand entries and a dense table is cut into pieces of T.
 #include <hip/hip_runtime.h>
 
+#include "okm_cmp_stage.h"
 #include "okm_dev_common.h"
 #include "okm_internal.h"
 #include "okm_search.h"
 
 namespace okm {
 
-constexpr int kCmpBlock = 256;
 constexpr uint32_t kCmpSlots = 256, kCmpSlotWords = 16;  // the merge's result slots: one 128-B line each
 #ifndef OKM_CMP_TILE  // a build flag, for the A/B in profiles/AB_LOG.md
 #define OKM_CMP_TILE 1024
@@ -209,30 +209,6 @@ __global__ __launch_bounds__(256) void k_cmp_bounds(const LookItem *__restrict__
     tiles[t] = w;
 }
 
-// A count as LDS holds it: u32, saturated.  kCmpSat from a u64 table means "fetch it" (a match then reads
-// the count itself from memory), so every form stages 4 bytes per count and has the same LDS footprint.
-constexpr uint32_t kCmpSat = 0xFFFFFFFFu;
-
-// n entries of a run into LDS, from entry `off` on: keys, and counts at counts[coff + off ...].  (One key
-// per lane and load: 16-byte loads of two keys, with the unaligned head and tail apart, measured 12 %
-// slower, profiles/AB_LOG.md.)
-template <typename KT, bool NARROW>
-__device__ __forceinline__ void cmp_stage(const LookItem *__restrict__ d, ull off, uint32_t n,
-                                          const uint64_t *__restrict__ counts, KT *lk, uint32_t *lc) {
-    const KT *kp = reinterpret_cast<const KT *>(gload(&d->keys)) + off;
-    const ull cb = gload(&d->coff) + off;
-    const uint32_t *c32 = reinterpret_cast<const uint32_t *>(counts);
-    for (uint32_t i = threadIdx.x; i < n; i += kCmpBlock) {
-        lk[i] = gload(kp + i);
-        if (NARROW) {
-            lc[i] = gload(c32 + cb + i);
-        } else {
-            const ull c = gload(counts + cb + i);
-            lc[i] = c < kCmpSat ? (uint32_t)c : kCmpSat;
-        }
-    }
-}
-
 // out[0] += keys in both tables whose counts pass both thresholds, out[1] +=
 // the sum of min(count_d, count_s) over them, out[2] += of count_d, out[3] +=
 // of count_s (all mod 2^64).  One workgroup per tile of D; workgroups past the
@@ -383,13 +359,18 @@ static void compare_tiles(hipStream_t s, const TableView &d, const TableView &sv
 #undef OKM_CMP_LAUNCH
 }
 
+void launch_compare_tile_offsets(void *stream, const TableView &d, uint32_t tile, unsigned long long *toff,
+                                 unsigned long long *scan_tmp) {
+    hipLaunchKernelGGL(k_cmp_tile_counts, dim3(d.max_runs / 256u + 1u), dim3(256), 0, (hipStream_t)stream, d.desc,
+                       d.n_desc, d.max_runs, tile, toff);
+    launch_exclusive_scan(stream, toff, toff, (uint64_t)d.max_runs + 1, scan_tmp);
+}
+
 void launch_compare(void *stream, const TableView &d, const TableView &sv, bool wide, uint64_t min_d, uint64_t min_s,
                     unsigned long long *toff, unsigned long long *scan_tmp, CmpTile *tiles, unsigned long long *out) {
     if (!d.max_runs || !sv.max_runs) return;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_cmp_tile_counts, dim3(d.max_runs / 256u + 1u), dim3(256), 0, s, d.desc, d.n_desc, d.max_runs,
-                       compare_tile(wide), toff);
-    launch_exclusive_scan(stream, toff, toff, (uint64_t)d.max_runs + 1, scan_tmp);
+    launch_compare_tile_offsets(stream, d, compare_tile(wide), toff, scan_tmp);
     if (wide)
         compare_tiles<K128>(s, d, sv, min_d, min_s, toff, tiles, out);
     else

@@ -3782,6 +3782,96 @@ okm_status okm_compare_counts(okm_ctx *a, okm_ctx *b, uint64_t min_count_a, uint
     return OKM_OK;
 }
 
+// Two counted tables merged into a third (okm_combine.hip), each read as a run
+// list cut at combine_tile.  The side with more entries drives; `swapped` tells
+// the kernels that a is the other one.  Pass 1 counts what every tile emits,
+// the total comes back with one sync, the output is taken from out's pool at
+// its exact size, pass 2 writes it.  A host-resident input is moved to the
+// device first (nothing here slices), so every reader has at most one slice.
+// All scratch comes from a's pool and runs on a's stream; b's and out's
+// streams are drained first.
+okm_status okm_combine_counts(okm_ctx *a, okm_ctx *b, okm_combine_op op, uint64_t min_count_a, uint64_t min_count_b,
+                              okm_ctx *out, uint64_t *n_out) {
+    if (!a || !b || !out) return fail(OKM_E_ARG, "okm_combine_counts: null context");
+    if (out == a || out == b) return fail(OKM_E_ARG, "okm_combine_counts: out is one of the inputs");
+    if ((int)op < OKM_COMBINE_UNION || (int)op > OKM_COMBINE_SUBTRACT)
+        return fail(OKM_E_ARG, "okm_combine_counts: unknown op " + std::to_string((int)op));
+    if (a->mode == OKM_MODE_SET || b->mode == OKM_MODE_SET || out->mode == OKM_MODE_SET)
+        return fail(OKM_E_STATE, "okm_combine_counts: a set-mode context has no counts");
+    if (a->k != b->k || a->wide != b->wide || a->k != out->k || a->wide != out->wide)
+        return fail(OKM_E_ARG, "okm_combine_counts: the contexts differ in k or in key width");
+    if (a->device != b->device || a->device != out->device)
+        return fail(OKM_E_ARG, "okm_combine_counts: the contexts are on different devices");
+    if (n_out) *n_out = 0;
+    min_count_a = std::max<uint64_t>(min_count_a, 1);
+    min_count_b = std::max<uint64_t>(min_count_b, 1);
+    HIP_TRY(hipSetDevice(a->device));
+    OKM_TRY(okm_reset(out));  // (synchronises out's stream)
+    OKM_TRY(okm_count(a, nullptr));
+    OKM_TRY(result_to_device(a));
+    if (b != a) {
+        OKM_TRY(okm_count(b, nullptr));
+        OKM_TRY(result_to_device(b));
+        OKM_TRY(sync(b));  // its table is read from a's stream
+    }
+    hipStream_t s = a->stream;
+    const bool a_drives = a->n_res >= b->n_res;
+    uint64_t n = 0, *ok = nullptr, *oc = nullptr;
+    if (a_drives ? a->n_res : b->n_res) {
+        Blocks scratch(*a->pool), table(*out->pool);
+        const uint32_t tile = combine_tile(a->wide);
+        TableReader A(a, TableForm::Runs, tile), B(b, TableForm::Runs, tile);
+        OKM_TRY(A.prepare(scratch));
+        OKM_TRY(B.prepare(scratch));
+        TableReader &D = a_drives ? A : B, &S = a_drives ? B : A;
+        const uint64_t max_tiles = compare_max_tiles(D.sl, D.max_runs, tile);
+        unsigned long long *toff = nullptr, *ttmp = nullptr, *tile_n = nullptr, *ntmp = nullptr;
+        CombTile *tiles = nullptr;
+        OKM_TRY(scratch.get((size_t)D.max_runs + 1, &toff));
+        OKM_TRY(scratch.get(scan_tmp_elems((uint64_t)D.max_runs + 1), &ttmp));
+        OKM_TRY(scratch.get(max_tiles, &tiles));
+        OKM_TRY(scratch.get(max_tiles + 1, &tile_n));
+        OKM_TRY(scratch.get(scan_tmp_elems(max_tiles + 1), &ntmp));
+        HIP_TRY(hipMemsetAsync(tile_n, 0, (max_tiles + 1) * sizeof(unsigned long long), s));
+        const uint64_t min_d = a_drives ? min_count_a : min_count_b, min_s = a_drives ? min_count_b : min_count_a;
+        a->timer.begin(s);
+        D.index(s, 0);
+        S.index(s, 0);
+        const TableView vd = D.view(0), vs = S.view(0);
+        launch_combine_count(s, vd, vs, a->wide, (int)op, !a_drives, min_d, min_s, toff, ttmp, tiles, tile_n, ntmp);
+        unsigned long long total = 0;
+        okm_status st = hipGetLastError() == hipSuccess ? OKM_OK : fail(OKM_E_DEVICE, "okm_combine_counts: launch");
+        if (st == OKM_OK && hipMemcpyAsync(&total, tile_n + max_tiles, sizeof(total), hipMemcpyDeviceToHost, s) != hipSuccess)
+            st = fail(OKM_E_DEVICE, "okm_combine_counts: device-to-host copy");
+        if (st == OKM_OK) st = sync(a);
+        n = total;
+        if (st == OKM_OK && n) {
+            if (table.get(n * a->kw, &ok) != OKM_OK || table.get(n, &oc) != OKM_OK)
+                st = fail(OKM_E_NOMEM, "okm_combine_counts: no device memory for the result's " + std::to_string(n) +
+                                           " entries");
+            else
+                launch_combine_write(s, vd, vs, a->wide, (int)op, !a_drives, min_d, min_s, toff, tiles, tile_n, ok, oc);
+        }
+        // both inputs read twice, the output written once
+        const auto view_bytes = [&](const TableView &v) { return (8.0 * a->kw + (v.narrow ? 4.0 : 8.0)) * (double)v.n; };
+        a->timer.end(s, "combine_counts", 2.0 * (view_bytes(vd) + view_bytes(vs)) + (8.0 * a->kw + 8.0) * (double)n);
+        OKM_TRY(st);
+        HIP_TRY(hipGetLastError());
+        OKM_TRY(sync(a));
+        scratch.free_all();
+        table.disown(ok);  // published: out's result owns both from here
+        table.disown(oc);
+    }
+    out->res_keys = ok;
+    out->res_counts = oc;
+    out->n_res = n;
+    out->info.distinct = n;
+    out->counted = true;
+    out->res_is_input = n > 0;  // the table stands for out's input: kept on its next add
+    if (n_out) *n_out = n;
+    return OKM_OK;
+}
+
 // Per-record depths of reads against the table, searched as okm_lookup_counts
 // searches it (TableForm::Search).  One launch sequence per (slice, batch):
 //   [launch_lookup_index, the first time]  k_depth_sep_count  scan

@@ -393,6 +393,36 @@ void launch_compare(void *stream, const TableView &d, const TableView &s, bool w
                     unsigned long long *toff, unsigned long long *scan_tmp, CmpTile *tiles, unsigned long long *out);
 size_t compare_slot_words();
 void launch_compare_fold(void *stream, const unsigned long long *slots, unsigned long long *out4);
+// toff[r] = tiles of `tile` entries in d's runs before run r (toff[d.max_runs] = tiles in all): toff = d.max_runs + 1
+// words, scan_tmp = scan_tmp_elems(d.max_runs + 1).
+void launch_compare_tile_offsets(void *stream, const TableView &d, uint32_t tile, unsigned long long *toff,
+                                 unsigned long long *scan_tmp);
+
+// Table combine (okm_combine.hip): two counted tables merged into a sorted
+// (key, u64 count) table; op is an okm_combine_op, d drives (the larger
+// table), swapped: the call's left table a is s.  Views are run lists cut at
+// combine_tile(wide); an empty s is a view of no runs.
+// One tile of the driving table and where its range of the other table ends
+// (it begins where the tile before ends; k_comb_bounds).
+struct CombTile {
+    uint32_t d_run, d_len;
+    uint64_t d_off;
+    uint32_t s_run1, pad_;
+    uint64_t s_off1;
+};
+uint32_t combine_tile(bool wide);
+// Pass 1.  Scratch: toff / scan_tmp as launch_compare_tile_offsets, tiles =
+// M = compare_max_tiles(d.n, d.max_runs, combine_tile(wide)), tile_n = M + 1
+// words zeroed by the caller, tile_scan_tmp = scan_tmp_elems(M + 1).
+// Afterwards tile_n[t] = the output offset of tile t and tile_n[M] = the
+// output's entries.
+void launch_combine_count(void *stream, const TableView &d, const TableView &s, bool wide, int op, bool swapped,
+                          uint64_t min_d, uint64_t min_s, unsigned long long *toff, unsigned long long *scan_tmp,
+                          CombTile *tiles, unsigned long long *tile_n, unsigned long long *tile_scan_tmp);
+// Pass 2, with pass 1's toff, tiles and tile offsets: okeys / ocounts hold tile_n[M] entries.
+void launch_combine_write(void *stream, const TableView &d, const TableView &s, bool wide, int op, bool swapped,
+                          uint64_t min_d, uint64_t min_s, const unsigned long long *toff, const CombTile *tiles,
+                          unsigned long long *tile_off, uint64_t *okeys, uint64_t *ocounts);
 
 // Per-record k-mer depth (okm_depth.hip): one scan of a device batch (records
 // joined by separators, 16-byte aligned, n bytes) against one representation

@@ -432,6 +432,29 @@ class KmerCounter:
               "okm_compare_counts")
         return {f: int(getattr(cc, f)) for f, _ in _lib.CountCompare._fields_}
 
+    def combine(self, other: "KmerCounter", op: str, min_count: int = 1, other_min_count: int = 1,
+                out: Optional["KmerCounter"] = None) -> "KmerCounter":
+        """This table (a) and other's (b) merged where they lie into a third
+        counted table (okm_combine_counts), returned as a KmerCounter (`out`,
+        reset first, or a new one of the same k, width and device).  op:
+        'union' (count_a + count_b), 'intersect' (min), 'intersect_left'
+        (count_a), 'difference' (a's keys that b does not hold), 'subtract'
+        (count_a - count_b, entries <= 0 dropped), over the entries with count
+        >= min_count / other_min_count.  Later add_* calls add to the table."""
+        if op not in _lib.COMBINE_OPS:
+            raise ValueError(f"combine: op {op!r} is not one of {sorted(_lib.COMBINE_OPS)}")
+        made = out is None
+        if made:
+            out = KmerCounter(self.k, "count", self.device, wide=self.wide)
+        try:
+            check(lib().okm_combine_counts(self.ctx, other.ctx, _lib.COMBINE_OPS[op], min_count, other_min_count,
+                                           out.ctx, None), "okm_combine_counts")
+        except Exception:
+            if made:
+                out.close()
+            raise
+        return out
+
     def read_depths(self, seqs: Sequence[bytes], min_count: int = 2, normalized: bool = False) -> np.ndarray:
         """One row per record (READ_DEPTH_DTYPE: windows, present, solid, sum,
         min, max): how deep the record's k-mers lie in the counted table,

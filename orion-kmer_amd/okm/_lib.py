@@ -32,6 +32,9 @@ OKM_E_RECORD = 9
 OKM_E_STATE = 10
 OKM_E_FORMAT = 11
 
+# okm_combine_op, by the names KmerCounter.combine takes
+COMBINE_OPS = {"union": 0, "intersect": 1, "intersect_left": 2, "difference": 3, "subtract": 4}
+
 OKM_MODE_COUNT = 0
 OKM_MODE_SET = 1
 OKM_MODE_WIDE = 0x100  # flag: k in 33..64 (two-u64 keys)
@@ -188,6 +191,7 @@ PROTOTYPES = {
     "okm_lookup_counts": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_int, _P64]),
     "okm_group_lookup_counts": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, _P64]),
     "okm_compare_counts": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, POINTER(CountCompare)]),
+    "okm_combine_counts": (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_void_p, POINTER(c_uint64)]),
     "okm_read_depths": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_uint64, c_void_p]),
     "okm_read_depths_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_uint64, c_void_p]),
     "okm_group_read_depths": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_uint64, c_void_p]),

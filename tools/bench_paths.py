@@ -37,6 +37,8 @@ input, warmup then timed steps bracketed by device syncs).
                      caller did before it: the gather (compact_items) plus
                      torch.searchsorted and an index of the counts; then the
                      same pair over the dense table, without the gather.
+  --workload combine okm_combine_counts (union, difference) of two counted
+                     configs[1]-sized tables against gather + torch + count.
   --workload compare okm_compare_counts of two counted configs[1]-sized tables
                      (two read seeds of one genome), both pending and both
                      dense, against the composition used before in the same
@@ -455,6 +457,111 @@ def wl_compare(args):
             "roofline": {"bound": "memory (both tables' keys and counts, once)", "kernel": "compare_counts (all launches)",
                          "alg_bytes_per_step": alg, "achieved": round(alg / (pend["median"] * 1e-3) / 1e9, 1),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s"}}
+
+
+def wl_combine(args):
+    """okm_combine_counts (union and difference) of two counted C2-sized tables
+    (wl_compare's) against what a caller composed before: result_device() of
+    both (the gathers), the set algebra in torch on the device (union: cat,
+    unique with inverse, index_add; difference: searchsorted and a mask), then
+    add_pairs_device + count into a third context.  Each repeat counts both
+    batches again (both tables pending), times the in-place combines, then the
+    compositions (which leave both dense), then the combines over two dense
+    tables.  The tables of the three are asserted equal."""
+    import torch
+    k, repeats, ops = 31, 3, ("union", "difference")
+    steps = max(args.steps, 5)
+    bufs = []
+    for seed in (2, 12):
+        b = okm.synth_reads(READS, READ_LEN, genome_len=GENOME_BP, genome_seed=2, seed=seed, sub_rate=0.001, n_rate=0.0001)
+        bufs.append((okm.DeviceBuffer(len(b)), len(b)))
+        bufs[-1][0].upload(b)
+        del b
+
+    def stat(c, name):
+        return dict(c.kernel_stats().get(name, {"launches": 0, "total_ms": 0.0, "alg_bytes": 0.0}))
+
+    def table(c):
+        pk, pc, n = c.result_device()
+        return torch.as_tensor(_DevView(pk, n), device="cuda"), torch.as_tensor(_DevView(pc, n), device="cuda")
+
+    def combine_ms(a, b, out, op):
+        for _ in range(args.warmup):
+            a.combine(b, op, out=out)
+        s0 = stat(a, "combine_counts")
+        t = time.perf_counter()
+        for _ in range(steps):
+            a.combine(b, op, out=out)
+        wall = (time.perf_counter() - t) * 1e3 / steps
+        s1 = stat(a, "combine_counts")
+        assert s1["launches"] - s0["launches"] == steps
+        return (s1["total_ms"] - s0["total_ms"]) / steps, wall, (s1["alg_bytes"] - s0["alg_bytes"]) / steps
+
+    def composed(a, b, third, op):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        (ak, ac), (bk, bc) = table(a), table(b)
+        if op == "union":
+            uk, inv = torch.unique(torch.cat((ak, bk)), return_inverse=True)
+            uc = torch.zeros_like(uk).index_add_(0, inv, torch.cat((ac, bc)))
+        else:
+            pos = torch.searchsorted(bk, ak).clamp_(max=len(bk) - 1)
+            keep = bk[pos] != ak
+            uk, uc = ak[keep], ac[keep]
+        torch.cuda.synchronize()
+        third.reset()
+        third.add_pairs_device(uk.data_ptr(), uc.data_ptr(), len(uk))
+        third.count()
+        return (time.perf_counter() - t) * 1e3
+
+    rows = []
+    with okm.KmerCounter(k) as a, okm.KmerCounter(k) as b, okm.KmerCounter(k) as out, okm.KmerCounter(k) as third:
+        for rep in range(repeats):
+            for c, (buf, n) in zip((a, b), bufs):
+                c.reset()
+                c.add_device_batch(buf.address, n)
+                c.count()
+                c.set_timing(True)
+            g0 = stat(a, "compact_items")["launches"] + stat(b, "compact_items")["launches"]
+            row = {}
+            for op in ops:
+                row[op + "_pending_ms"], row[op + "_pending_wall_ms"], row[op + "_alg_bytes"] = combine_ms(a, b, out, op)
+            assert stat(a, "compact_items")["launches"] + stat(b, "compact_items")["launches"] == g0, "the combine gathered"
+            for op in ops:  # (the first composition pays both gathers; the second finds the tables dense)
+                row[op + "_before_wall_ms"] = composed(a, b, third, op)
+                a.combine(b, op, out=out)
+                assert all(torch.equal(x, y) for x, y in zip(table(out), table(third))), op
+                row[op + "_entries"] = out.count()
+            for op in ops:
+                row[op + "_dense_ms"], row[op + "_dense_wall_ms"], _ = combine_ms(a, b, out, op)
+            rows.append(row)
+            log(json.dumps(row))
+    for buf, _ in bufs:
+        buf.free()
+
+    def col(name):
+        v = sorted(r[name] for r in rows)
+        return {"median": round(v[len(v) // 2], 4), "min": round(v[0], 4), "max": round(v[-1], 4)}
+
+    alg = rows[0]["union_alg_bytes"]
+    res = {"metric": "two counted C2 tables (k=31) combined into a third (union) where they lie on one MI355X, HIP-event ms",
+           "value": col("union_pending_ms")["median"], "unit": "ms", "n_gpus": 1, "steps": steps, "warmup": args.warmup,
+           "higher_is_better": False, "dtype": "u64 keys, u32 staged counts, u64 counts out",
+           "data": "synthetic (BASELINE configs[1] reads and a second read seed of the same genome, device-resident)",
+           "config": {"workload": "combine: 2 x 3,355,443 x 150 bp reads counted into two tables", "k": k, "repeats": repeats,
+                      "lib": os.path.basename(os.path.dirname(os.environ.get("OKM_LIB", ""))) or "build"},
+           "repeats": rows,
+           "roofline": {"bound": "memory (both tables read twice, the output written once)",
+                        "kernel": "combine_counts (all launches)", "alg_bytes_per_step": alg,
+                        "achieved": round(alg / (col("union_pending_ms")["median"] * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s"}}
+    for op in ops:
+        res[op] = {"entries": rows[0][op + "_entries"], "pending_ms": col(op + "_pending_ms"),
+                   "pending_wall_ms": col(op + "_pending_wall_ms"), "dense_ms": col(op + "_dense_ms"),
+                   "dense_wall_ms": col(op + "_dense_wall_ms"), "before_wall_ms": col(op + "_before_wall_ms"),
+                   "pending_wall_over_before": round(col(op + "_pending_wall_ms")["median"] /
+                                                     col(op + "_before_wall_ms")["median"], 4)}
+    return res
 
 
 def wl_depth(args):
@@ -1082,7 +1189,7 @@ def wl_classify(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth", "compare"],
+    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth", "compare", "combine"],
                     required=True)
     ap.add_argument("--no-ref", action="store_true", help="c3: skip the one-GPU reference table")
     ap.add_argument("--c3-reads", type=int, default=C3_READS,
@@ -1107,7 +1214,7 @@ def main():
     c5 = wl_c5_dist if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.loopback else wl_c5
     out = {"query": wl_query, "build": wl_build, "wide": wl_wide, "classify": wl_classify,
            "c5": c5, "c3": wl_c3_loop, "histogram": wl_histogram, "lookup": wl_lookup, "depth": wl_depth,
-           "compare": wl_compare}[args.workload](args)
+           "compare": wl_compare, "combine": wl_combine}[args.workload](args)
     if out is not None:
         print(json.dumps(out), flush=True)
 
