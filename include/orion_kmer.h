@@ -238,6 +238,48 @@ okm_status okm_read_depths(okm_ctx *ctx, const uint8_t *seq, const uint64_t *off
 okm_status okm_read_depths_device(okm_ctx *ctx, const uint8_t *d_seq, uint64_t n_bytes, uint64_t n_records,
                                   uint64_t min_count, okm_read_depth *d_out /* device, n_records */);
 
+/* Per-record solid runs: WHERE in each record the solid k-mers lie -- what a
+ * k-mer-spectrum trimmer needs (Quake, BFC and Lighter keep the longest solid
+ * stretch, khmer trim-low-abund cuts at the first weak k-mer); an extension,
+ * the reference has none.  Slot j of a record is the window that starts at its
+ * base j (after normalisation); a slot is solid when its window holds A/C/G/T
+ * only (either case, U as T), its canonical k-mer is in the table and its
+ * count is at least min_count (0 behaves as 1).  `solid` is okm_read_depth's
+ * `solid` by definition.  The bases each trimming rule keeps:
+ *   the longest solid stretch   [run_start, run_start + run_len + k - 1)   when run_len > 0
+ *   khmer's prefix rule         [0, lead + k - 1)                          when lead > 0
+ * The rows are found on the device from two bit planes of one bit per batch
+ * byte (solid slots, separators); the read bytes are searched once and the
+ * table stays where and as it lies, as for okm_read_depths.
+ * There is no group form: rows taken against owners of disjoint key ranges do
+ * not combine by any rule on the rows (a run may alternate between owners),
+ * only by OR-ing the owners' solid bit planes, which never leave the device. */
+typedef struct okm_solid_run {
+    uint64_t slots;      /* window positions of the record: len - k + 1, or 0 when len < k (len after normalisation) */
+    uint64_t solid;      /* slots whose window is valid, in the table, and has count >= min_count */
+    uint64_t run_start;  /* first slot (0-based) of the longest run of consecutive solid slots; the earliest of equals; 0 when run_len == 0 */
+    uint64_t run_len;    /* its length in slots; 0 when solid == 0 */
+    uint64_t lead;       /* solid slots from slot 0 up to the first slot that is not solid */
+    uint64_t trail;      /* the same from the last slot backwards */
+} okm_solid_run;
+/* out[r] = the solid runs of record r.  Everything else as okm_read_depths:
+ * the record layout and `normalized`, every record gets a row (zeros when it
+ * is empty or shorter than k), counts first if batches are pending, read-only
+ * on the table in every representation, host records go up in chunks of whole
+ * records.  An empty table: slots as they are, zeros elsewhere.  n_records ==
+ * 0: OK, nothing touched.  A set-mode context has no counts: OKM_E_STATE.
+ * One chunk -- so in effect one record -- of 2^32 bytes or more: OKM_E_ARG
+ * (positions in a batch are 32 bits on the device). */
+okm_status okm_read_solid_runs(okm_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, uint64_t n_records,
+                               int normalized, uint64_t min_count, okm_solid_run *out /* host, n_records */);
+/* The same over a device batch, as okm_read_depths_device takes it (a record's
+ * index is the number of separators before it, records past n_records are
+ * dropped and rows past the last record are zero, an unterminated last record
+ * is taken as it stands, bytes at and beyond n_bytes are never looked at).
+ * n_bytes >= 2^32: OKM_E_ARG (batch too large). */
+okm_status okm_read_solid_runs_device(okm_ctx *ctx, const uint8_t *d_seq, uint64_t n_bytes, uint64_t n_records,
+                                      uint64_t min_count, okm_solid_run *d_out /* device, n_records */);
+
 /* Two counted tables compared: the keys both hold, with their counts -- what
  * `kmc_tools simple intersect` with counters_min, or two jellyfish tables,
  * answer; an extension, the reference's compare works on keys alone.  An entry

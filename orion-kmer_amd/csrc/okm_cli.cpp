@@ -219,7 +219,7 @@ static const char *kVersion = "orion-kmer 0.1.0";
 
 static void print_help(const std::string &cmd) {
     if (cmd == "count")
-        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n      --depth <FASTX>              Take the k-mer depth of every record of FASTX in the whole table (extension)\n      --depth-output <FILE>        Where --depth writes id<TAB>windows<TAB>present<TAB>solid<TAB>sum<TAB>min<TAB>max, in input order\n      --depth-min-count <N>        A window is solid when its k-mer's count is at least N [default: 2]\n      --compare <FASTX>            Count FASTX as a second table (same k) and compare the two tables with their counts (extension)\n      --compare-output <FILE>      Where --compare writes field<TAB>value: the shared k-mers, their counts, Jaccard, weighted Jaccard, Bray-Curtis\n      --compare-min-count <N>      Minimum count of a k-mer of the --compare table (--min-count: of the first table) [default: 1]\n      --combine <FASTX>            Count FASTX as a second table (same k) and combine the two tables into a third (extension)\n      --combine-op <OP>            union, intersect, intersect_left, difference or subtract (the first table is the left one)\n      --combine-output <FILE>      Where --combine writes the combined table as KMER<TAB>COUNT lines\n      --combine-min-count <N>      Minimum count of a k-mer of the --combine table (--min-count: of the first table) [default: 1]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
+        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n      --depth <FASTX>              Take the k-mer depth of every record of FASTX in the whole table (extension)\n      --depth-output <FILE>        Where --depth writes id<TAB>windows<TAB>present<TAB>solid<TAB>sum<TAB>min<TAB>max, in input order\n      --depth-min-count <N>        A window is solid when its k-mer's count is at least N [default: 2]\n      --solid-runs <FASTX>         Find the solid runs of every record of FASTX in the whole table: where its solid k-mers lie (extension)\n      --solid-runs-output <FILE>   Where --solid-runs writes id<TAB>slots<TAB>solid<TAB>run_start<TAB>run_len<TAB>lead<TAB>trail, in input order\n      --solid-runs-min-count <N>   A slot is solid when its k-mer's count is at least N [default: 2]\n      --compare <FASTX>            Count FASTX as a second table (same k) and compare the two tables with their counts (extension)\n      --compare-output <FILE>      Where --compare writes field<TAB>value: the shared k-mers, their counts, Jaccard, weighted Jaccard, Bray-Curtis\n      --compare-min-count <N>      Minimum count of a k-mer of the --compare table (--min-count: of the first table) [default: 1]\n      --combine <FASTX>            Count FASTX as a second table (same k) and combine the two tables into a third (extension)\n      --combine-op <OP>            union, intersect, intersect_left, difference or subtract (the first table is the left one)\n      --combine-output <FILE>      Where --combine writes the combined table as KMER<TAB>COUNT lines\n      --combine-min-count <N>      Minimum count of a k-mer of the --combine table (--min-count: of the first table) [default: 1]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
     else if (cmd == "build")
         printf("Build a unique k-mer database from genome assemblies\n\nUsage: orion-kmer build [OPTIONS] --kmer-size <KMER_SIZE> --genomes <GENOME_FILES>... --output-file <OUTPUT_FILE>\n");
     else if (cmd == "compare")
@@ -437,6 +437,39 @@ static int write_depths(okm_group *grp, okm_reader *r, const std::string &path, 
     return 0;
 }
 
+// --solid-runs: every batch of the reader through okm_read_solid_runs on the
+// one GPU's table, one line per record in input order: id, slots, solid,
+// run_start, run_len, lead, trail.
+static int write_solid_runs(okm_ctx *ctx, okm_reader *r, const std::string &path, const std::string &out_path,
+                            uint64_t min_count) {
+    std::string lines;
+    std::vector<okm_solid_run> rows;
+    for (;;) {
+        const uint8_t *seq, *ids;
+        const uint64_t *off, *ioff;
+        uint64_t n;
+        if (okm_reader_next(r, 128ull << 20, &seq, &off, &n) != OKM_OK)
+            return die("Error reading record from " + path);
+        if (n == 0) break;
+        okm_reader_ids(r, &ids, &ioff);
+        rows.resize(n);
+        if (!ctx || okm_read_solid_runs(ctx, seq, off, n, 1, min_count, rows.data()) != OKM_OK)
+            return die("GPU engine failure while finding solid runs: " + err_detail());
+        for (uint64_t i = 0; i < n; ++i) {
+            lines.append(reinterpret_cast<const char *>(ids + ioff[i]), ioff[i + 1] - ioff[i]);
+            const okm_solid_run &d = rows[i];
+            for (uint64_t v : {d.slots, d.solid, d.run_start, d.run_len, d.lead, d.trail}) {
+                lines += '\t';
+                lines += std::to_string(v);
+            }
+            lines += '\n';
+        }
+    }
+    if (okm_write_file(out_path.c_str(), reinterpret_cast<const uint8_t *>(lines.data()), lines.size()) != OKM_OK)
+        return die("Failed to get output writer for solid runs output file: " + dbg_path(out_path));
+    return 0;
+}
+
 // --compare: the second input counted into a context of its own beside the
 // first table's (one GPU), okm_compare_counts of the two, and field<TAB>value
 // lines: the eight fields, then the ratios that follow from them, printed with
@@ -539,6 +572,22 @@ static int run_count(const Args &a) {
     uint64_t depth_min = 2;
     if (get_one(a, "depth-min-count", dm) && (!parse_u64(dm, depth_min) || depth_min == 0))
         return usage_error("invalid value '" + dm + "' for '--depth-min-count <N>'");
+    // --solid-runs <FASTX> --solid-runs-output <FILE> [--solid-runs-min-count
+    // <N>]: per record of FASTX, where its solid k-mers lie in the WHOLE table
+    // (what a k-mer-spectrum trimmer cuts by; an extension); the two flags need
+    // one another and the min-count flag needs them.  One GPU only: the owners'
+    // rows do not combine.
+    std::string sr_path, sr_out, srm;
+    const bool want_sr = get_one(a, "solid-runs", sr_path), has_srout = get_one(a, "solid-runs-output", sr_out);
+    const bool has_srmin = get_one(a, "solid-runs-min-count", srm);
+    if (want_sr != has_srout || (has_srmin && !want_sr))
+        return usage_error(std::string("the following required arguments were not provided:\n  ") +
+                           (want_sr ? "--solid-runs-output <FILE>" : "--solid-runs <FASTX>"));
+    uint64_t sr_min = 2;
+    if (has_srmin && (!parse_u64(srm, sr_min) || sr_min == 0))
+        return usage_error("invalid value '" + srm + "' for '--solid-runs-min-count <N>'");
+    if (want_sr && g_gpus != 1)
+        return usage_error("the argument '--solid-runs <FASTX>' cannot be used with '--gpus <GPUS>' other than 1");
     // --compare <FASTX> --compare-output <FILE> [--compare-min-count <N>]: FASTX
     // is counted at the same k into a second table and the two tables are
     // compared with their counts (kmc_tools intersect with counters_min; an
@@ -603,6 +652,12 @@ static int run_count(const Args &a) {
         if (ds == OKM_E_IO) return die("Failed to get input reader for depth file: " + dbg_path(depth_path));
         if (ds != OKM_OK) return die("Failed to parse FASTA/Q content from depth file: " + dbg_path(depth_path));
     }
+    DepthReader solid_reader;  // the --solid-runs reads, opened as the depth reads are
+    if (want_sr) {
+        const okm_status ds = okm_reader_open2(&solid_reader.r, sr_path.c_str(), 1, OKM_READ_IDS);
+        if (ds == OKM_E_IO) return die("Failed to get input reader for solid runs file: " + dbg_path(sr_path));
+        if (ds != OKM_OK) return die("Failed to parse FASTA/Q content from solid runs file: " + dbg_path(sr_path));
+    }
     // one table across all inputs (count.rs:48), on g_gpus GPUs (default 1),
     // started while the first input is parsed
     phase("start");
@@ -650,6 +705,11 @@ static int run_count(const Args &a) {
         if ((rc = write_depths(grp, depth_reader.r, depth_path, depth_out, depth_min))) return rc;
         info("orion_kmer::commands::count", "Successfully wrote the read depths to " + dbg_path(depth_out));
         phase("depth");
+    }
+    if (want_sr) {  // the reads go to two bit planes and those to the rows; the table stays as it lies
+        if ((rc = write_solid_runs(okm_group_owner(grp, 0), solid_reader.r, sr_path, sr_out, sr_min))) return rc;
+        info("orion_kmer::commands::count", "Successfully wrote the solid runs to " + dbg_path(sr_out));
+        phase("solid runs");
     }
     if (want_cmp) {  // both tables are merged as their counts left them
         if ((rc = write_compare(okm_group_owner(grp, 0), k, wide, cmp_path, cmp_out, min_count, cmp_min))) return rc;
@@ -1214,6 +1274,9 @@ int main(int argc, char **argv) {
         spec.push_back({"depth", 0, true, false});
         spec.push_back({"depth-output", 0, true, false});
         spec.push_back({"depth-min-count", 0, true, false});
+        spec.push_back({"solid-runs", 0, true, false});
+        spec.push_back({"solid-runs-output", 0, true, false});
+        spec.push_back({"solid-runs-min-count", 0, true, false});
         spec.push_back({"compare", 0, true, false});
         spec.push_back({"compare-output", 0, true, false});
         spec.push_back({"compare-min-count", 0, true, false});

@@ -23,6 +23,7 @@
 // round at the end of the launch sequence: min = present ? ~field : 0.
 #include <hip/hip_runtime.h>
 
+#include "okm_depth_keys.h"
 #include "okm_dev_common.h"
 #include "okm_internal.h"
 #include "okm_scan.h"
@@ -42,6 +43,7 @@ constexpr int kDepthBlock = 256;
 // (window starts + a 32 or 64 byte halo), so 16 is the smallest run; a longer
 // one only adds loaded words to carry (24 at k > 32 already).
 constexpr int kDepthSeg = 16;
+static_assert(kDepthSeg == kKeySeg, "DepthKeys (okm_depth_keys.h) is built for this run");
 constexpr int kDepthTile = kDepthBlock * kDepthSeg;  // 4096 bytes per workgroup
 // Searches a lane keeps in flight.  One, as in the lookup (okm_lookup.hip
 // kLookFly): the kernel is bound by the memory system's rate of random 64-byte
@@ -84,42 +86,6 @@ __global__ __launch_bounds__(kDepthBlock) void k_depth_sep_count(const uint8_t *
     block_excl_scan<kDepthBlock>((ull)c, wsum, &tot);
     if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
 }
-
-// A key type's side of the scan: the halo its windows need, the valid windows
-// of the thread's run and the canonical key of window j.
-template <typename KT> struct DepthKeys;
-template <> struct DepthKeys<ull> {
-    static constexpr int kHalo = 32;
-    static constexpr int kNP = WinWords<kDepthSeg, 32>::kLoad / 16;
-    __device__ static __forceinline__ uint32_t valid_mask(const Codes<kNP> &c, uint32_t k) {
-        return ~invalid_windows<kDepthSeg, kNP>(c, k) & ((1u << kDepthSeg) - 1u);
-    }
-    // window_key_nv's value from 64-bit slices: with k known only at run time
-    // its 32-bit funnel shifts index the code words by k, which puts them in
-    // scratch memory (as k_query_hits<0> has them); here only j, a
-    // compile-time constant, picks words, and the kernel waits on its
-    // searches, not on these shifts.
-    __device__ static __forceinline__ ull key(const Codes<kNP> &c, int j, uint32_t k) {
-        const uint64_t f = fwd_top64(c, j) >> (64u - 2u * k);                               // kmer.rs:37-57
-        const uint64_t r = rc_low64(c, j) & (k >= 32 ? ~0ull : ((1ull << (2u * k)) - 1ull));  // kmer.rs:79-94
-        return f < r ? f : r;                                                                // kmer.rs:99-106
-    }
-};
-template <> struct DepthKeys<K128> {
-    static constexpr int kHalo = 64;
-    static constexpr int kNP = WinWords<kDepthSeg, 64>::kLoad / 16;
-    __device__ static __forceinline__ uint32_t valid_mask(const Codes<kNP> &c, uint32_t k) {
-        const uint64_t km = k >= 64 ? ~0ull : ((1ull << k) - 1ull);
-        uint32_t m = 0;
-#pragma unroll
-        for (int j = 0; j < kDepthSeg; ++j) m |= ((bad_low64(c, j) & km) == 0 ? 1u : 0u) << j;
-        return m;
-    }
-    __device__ static __forceinline__ K128 key(const Codes<kNP> &c, int j, uint32_t k) {
-        bool valid;
-        return window_key128(c, j, k, &valid);
-    }
-};
 
 // What a thread has seen of the record it is in.
 struct DepthAcc {

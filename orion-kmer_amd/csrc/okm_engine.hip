@@ -3996,6 +3996,128 @@ okm_status okm_read_depths(okm_ctx *c, const uint8_t *seq, const uint64_t *offse
     return OKM_OK;
 }
 
+// Per-record solid runs of reads against the table, searched as the depth
+// reader searches it.  Per batch (a device batch, or one chunk of host
+// records, cut as okm_read_depths cuts them):
+//   for every slice:  [launch_lookup_index, the first time]  k_solid_mask
+//   then once:        k_runs_init  k_runs_tiles  scan  k_runs_carry  k_runs_rows  k_runs_fix
+// The slices of a host-resident table meet in the solid bit plane (OR), not in
+// the rows, so the chunk loop is the OUTER one here: a chunk's planes stay on
+// the device until the last slice has added its hits.  The price is that a
+// sliced table goes up once per chunk, not once per call: (chunks - 1) further
+// uploads of the table's 16 or 24 bytes per entry, against 32 MiB of reads a
+// chunk.  Only a host-resident table pays it; every other representation is
+// searched where it lies.  (Keeping every chunk's planes, n / 4 bytes in all,
+// would let the table go up once; it would also make the call's footprint
+// grow with its input, which the chunking is there to prevent.)
+namespace {
+struct SolidCall {
+    okm_ctx *c;
+    Blocks scratch;
+    TableReader tab;
+    uint64_t nslices;  // searches per batch
+    unsigned long long *planes = nullptr, *tiles = nullptr;
+    explicit SolidCall(okm_ctx *ctx)
+        : c(ctx), scratch(*ctx->pool), tab(ctx, TableForm::Search), nslices(std::max<uint64_t>(tab.nslices, 1)) {}
+    // the table's side of the scratch, the bit planes and the tile words of a batch of at most max_bytes
+    okm_status prepare(uint64_t max_bytes) {
+        OKM_TRY(tab.prepare(scratch));
+        const uint64_t nt = solid_tiles(max_bytes);
+        OKM_TRY(scratch.get(2 * solid_plane_words(max_bytes), &planes));
+        OKM_TRY(scratch.get(4 * nt + scan_tmp_elems(nt) + 1, &tiles));
+        return OKM_OK;
+    }
+    // one device batch against every slice, into rows (device; every row is written)
+    okm_status batch(const uint8_t *d_seq, uint64_t nb, uint64_t nrec, uint64_t min_count, okm_solid_run *rows) {
+        for (uint64_t si = 0; si < nslices; ++si) {
+            OKM_TRY(tab.upload(c->stream, si));
+            c->timer.begin(c->stream);
+            tab.index(c->stream, si);
+            launch_solid_mask(c->stream, d_seq, nb, c->k, c->wide, tab.view(si), min_count, si == 0, planes);
+            // the read bytes in and the rows out, once per batch however many slices search it
+            c->timer.end(c->stream, "solid_mask", si == 0 ? (double)nb + 48.0 * (double)nrec : 0.0);
+        }
+        c->timer.begin(c->stream);
+        launch_solid_runs(c->stream, nb, nrec, c->k, planes, tiles, rows);
+        c->timer.end(c->stream, "solid_runs", 16.0 * (double)solid_plane_words(nb) + 48.0 * (double)nrec);
+        HIP_TRY(hipGetLastError());
+        return OKM_OK;
+    }
+};
+}  // namespace
+
+okm_status okm_read_solid_runs_device(okm_ctx *c, const uint8_t *d_seq, uint64_t n_bytes, uint64_t n_records,
+                                      uint64_t min_count, okm_solid_run *d_out) {
+    if (!c || (n_records && (!d_out || (!d_seq && n_bytes))))
+        return fail(OKM_E_ARG, "okm_read_solid_runs_device: null argument");
+    if (n_bytes >> 32 || n_records >> 40) return fail(OKM_E_ARG, "okm_read_solid_runs_device: batch too large");
+    if (c->mode == OKM_MODE_SET)
+        return fail(OKM_E_STATE, "okm_read_solid_runs_device: a set-mode context has no counts");
+    if (n_records == 0) return OKM_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    OKM_TRY(okm_count(c, nullptr));
+    if (n_bytes == 0) {  // records, all of them empty
+        HIP_TRY(hipMemsetAsync(d_out, 0, n_records * sizeof(okm_solid_run), c->stream));
+        return sync(c);
+    }
+    SolidCall d(c);
+    OKM_TRY(d.prepare(n_bytes));
+    const uint8_t *src = d_seq;
+    if ((reinterpret_cast<uintptr_t>(d_seq) & 15u) != 0) {  // the scan loads 16-B words
+        uint64_t *copy = nullptr;
+        OKM_TRY(d.scratch.get(n_bytes / 8 + 1, &copy));
+        HIP_TRY(hipMemcpyAsync(copy, d_seq, n_bytes, hipMemcpyDeviceToDevice, c->stream));
+        src = reinterpret_cast<const uint8_t *>(copy);
+    }
+    OKM_TRY(d.batch(src, n_bytes, n_records, min_count, d_out));
+    OKM_TRY(sync(c));
+    d.scratch.free_all();
+    return OKM_OK;
+}
+
+okm_status okm_read_solid_runs(okm_ctx *c, const uint8_t *seq, const uint64_t *offsets, uint64_t n_records,
+                               int normalized, uint64_t min_count, okm_solid_run *out) {
+    if (!c || (n_records && (!offsets || !out))) return fail(OKM_E_ARG, "okm_read_solid_runs: null argument");
+    if (n_records >> 40) return fail(OKM_E_ARG, "okm_read_solid_runs: more than 2^40 records");
+    if (c->mode == OKM_MODE_SET) return fail(OKM_E_STATE, "okm_read_solid_runs: a set-mode context has no counts");
+    if (n_records == 0) return OKM_OK;
+    if (offsets[n_records] != offsets[0] && !seq) return fail(OKM_E_ARG, "okm_read_solid_runs: null seq");
+    HIP_TRY(hipSetDevice(c->device));
+    OKM_TRY(okm_count(c, nullptr));
+    // chunks of whole records, as okm_read_depths cuts them: [first record, one past the last)
+    uint64_t chunk = kDepthChunk;
+    if (const int64_t e = test_knob(OKM_TEST_DEPTH_CHUNK); e > 0) chunk = (uint64_t)e;
+    std::vector<std::pair<uint64_t, uint64_t>> chunks;
+    uint64_t max_bytes = 0, max_recs = 0;
+    for (uint64_t r0 = 0; r0 < n_records;) {
+        uint64_t r1 = r0 + 1;  // at least one record, whatever its size
+        const auto bytes = [&](uint64_t e) { return offsets[e] - offsets[r0] + (e - r0); };
+        while (r1 < n_records && bytes(r1 + 1) <= chunk) ++r1;
+        if (bytes(r1) >> 32) return fail(OKM_E_ARG, "okm_read_solid_runs: batch too large (one record of 2^32 bytes)");
+        chunks.emplace_back(r0, r1);
+        max_bytes = std::max(max_bytes, bytes(r1));
+        max_recs = std::max(max_recs, r1 - r0);
+        r0 = r1;
+    }
+    SolidCall d(c);
+    OKM_TRY(d.prepare(max_bytes));
+    uint64_t *dseq = nullptr;
+    okm_solid_run *drows = nullptr;
+    OKM_TRY(d.scratch.get(max_bytes / 8 + 1, &dseq));
+    OKM_TRY(d.scratch.get(max_recs, &drows));
+    std::vector<uint8_t> packed(max_bytes);
+    for (const auto &ch : chunks) {
+        const uint64_t r0 = ch.first, nr = ch.second - ch.first;
+        const uint64_t nb = pack_records(packed.data(), seq, offsets, r0, ch.second, normalized);
+        HIP_TRY(hipMemcpyAsync(dseq, packed.data(), nb, hipMemcpyHostToDevice, c->stream));
+        OKM_TRY(d.batch(reinterpret_cast<const uint8_t *>(dseq), nb, nr, min_count, drows));
+        HIP_TRY(hipMemcpyAsync(out + r0, drows, nr * sizeof(okm_solid_run), hipMemcpyDeviceToHost, c->stream));
+        OKM_TRY(sync(c));  // `packed` is reused
+    }
+    d.scratch.free_all();
+    return OKM_OK;
+}
+
 okm_status okm_finish_counts(okm_ctx *c, uint64_t min_count, uint64_t **keys, uint64_t **counts, uint64_t *n) {
     if (!c || !keys || !n) return fail(OKM_E_ARG, "null argument");
     *keys = nullptr;

@@ -451,6 +451,23 @@ inline void depth_combine(okm_read_depth &a, const okm_read_depth &b) {
     a.sum += b.sum;
 }
 
+// Per-record solid runs (okm_solid.hip), in two stages over a device batch
+// (records joined by separators, 16-byte aligned, 0 < n < 2^32 bytes).
+// planes: 2 * solid_plane_words(n) words, the solid bit plane and then the
+// separator bit plane, one bit per batch byte.  launch_solid_mask searches one
+// representation of the table as launch_read_depths does: the batch's first
+// launch (`first`) writes both planes whole, every later one (a further slice
+// of a host-resident table) ORs its hits into the solid plane.
+// launch_solid_runs then turns the planes into rows[nrec] (r = separators
+// before the slot, rows past nrec dropped, every row written).  tiles:
+// 4 * solid_tiles(n) + scan_tmp_elems(solid_tiles(n)) words of scratch.
+uint64_t solid_tiles(uint64_t n_bytes);
+uint64_t solid_plane_words(uint64_t n_bytes);
+void launch_solid_mask(void *stream, const uint8_t *seq, uint64_t n, uint32_t k, bool wide, const TableView &t,
+                       uint64_t min_count, bool first, unsigned long long *planes);
+void launch_solid_runs(void *stream, uint64_t n, uint64_t nrec, uint32_t k, const unsigned long long *planes,
+                       unsigned long long *tiles, okm_solid_run *rows);
+
 // |A ∩ B| of sorted unique arrays (merge-path style binary search per element).
 void launch_intersect_count(void *stream, const uint64_t *a, uint64_t na, const uint64_t *b,
                             uint64_t nb, unsigned long long *out, bool wide);

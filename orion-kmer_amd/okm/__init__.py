@@ -163,6 +163,8 @@ class DeviceBuffer:
 
 # okm_read_depth (include/orion_kmer.h): six u64 per record
 READ_DEPTH_DTYPE = np.dtype([(f, "<u8") for f in ("windows", "present", "solid", "sum", "min", "max")])
+# okm_solid_run (include/orion_kmer.h): six u64 per record
+SOLID_RUN_DTYPE = np.dtype([(f, "<u8") for f in ("slots", "solid", "run_start", "run_len", "lead", "trail")])
 
 
 def pack_records(seqs: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
@@ -472,6 +474,25 @@ class KmerCounter:
         n_records rows of 48 bytes in device memory."""
         check(lib().okm_read_depths_device(self.ctx, c_void_p(d_seq), nbytes, n_records, min_count, c_void_p(d_out)),
               "okm_read_depths_device")
+
+    def solid_runs(self, seqs: Sequence[bytes], min_count: int = 2, normalized: bool = False) -> np.ndarray:
+        """One row per record (SOLID_RUN_DTYPE: slots, solid, run_start,
+        run_len, lead, trail): where the record's solid k-mers lie -- the
+        longest run of consecutive solid window positions and the solid runs
+        at its two ends (okm_read_solid_runs).  A trimmer that keeps the
+        longest solid stretch keeps bases [run_start, run_start + run_len +
+        k - 1); khmer's prefix rule keeps [0, lead + k - 1) when lead > 0."""
+        data, offs = pack_records(list(seqs))
+        out = np.zeros(len(offs) - 1, dtype=SOLID_RUN_DTYPE)
+        check(lib().okm_read_solid_runs(self.ctx, data.ctypes.data, offs.ctypes.data, len(out), 1 if normalized else 0,
+                                        min_count, out.ctypes.data), "okm_read_solid_runs")
+        return out
+
+    def solid_runs_device(self, d_seq: int, nbytes: int, n_records: int, d_out: int, min_count: int = 2) -> None:
+        """solid_runs() over a device batch (add_device_batch's layout) into
+        n_records rows of 48 bytes in device memory."""
+        check(lib().okm_read_solid_runs_device(self.ctx, c_void_p(d_seq), nbytes, n_records, min_count,
+                                               c_void_p(d_out)), "okm_read_solid_runs_device")
 
     def result_device(self) -> Tuple[int, int, int]:
         k = c_void_p()

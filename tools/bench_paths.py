@@ -48,6 +48,12 @@ input, warmup then timed steps bracketed by device syncs).
                      own counted table, pending and then dense, and in the same
                      process the yardstick: okm_lookup_counts of 2^24 device
                      queries on the same tables (windows/s against queries/s).
+  --workload solid_runs okm_read_solid_runs_device of the configs[1] batch
+                     against its own counted table, pending and then dense, and
+                     in the same process okm_read_depths_device over the same
+                     batch: the ratio of the two and stage 2's share, `solid`
+                     asserted equal; the line is appended to
+                     profiles/solid_runs.jsonl.
 
 The CPU baseline is the C restatement (oracle/) on a bounded sample, 1 thread.
 """
@@ -676,6 +682,85 @@ def wl_depth(args):
                          "peak": HBM_PEAK_GBS, "unit": "GB/s"}}
 
 
+def wl_solid_runs(args):
+    """Per-read solid runs of the C2 batch against its own table, pending and
+    then dense (result_device() gathers), beside okm_read_depths_device over
+    the same batch in the same process; every figure is a HIP-event time from
+    the engine's timer rows (solid_mask: stage 1, the search; solid_runs: stage
+    2, the bit planes to the rows).  `solid` must agree between the readers."""
+    k, min_count, repeats = 31, 2, 3
+    steps = max(args.steps, 5)
+    batch, nreads = c2_batch(), READS
+    dbuf = okm.DeviceBuffer(len(batch))
+    dbuf.upload(batch)
+    runs_buf, depth_buf = okm.DeviceBuffer(48 * nreads), okm.DeviceBuffer(48 * nreads)
+
+    def event_ms(c, names, fn):
+        for _ in range(args.warmup):
+            fn()
+        before = c.kernel_stats()
+        for _ in range(steps):
+            fn()
+        after = c.kernel_stats()
+        return [(after[n]["total_ms"] - before.get(n, {"total_ms": 0.0})["total_ms"]) / steps for n in names]
+
+    def runs():
+        c.solid_runs_device(dbuf.address, len(batch), nreads, runs_buf.address, min_count)
+
+    def depth():
+        c.read_depths_device(dbuf.address, len(batch), nreads, depth_buf.address, min_count)
+
+    def check():
+        a, b = np.empty(nreads, okm.SOLID_RUN_DTYPE), np.empty(nreads, okm.READ_DEPTH_DTYPE)
+        runs_buf.download(a)
+        depth_buf.download(b)
+        assert np.array_equal(a["solid"], b["solid"]), "solid differs between the two readers"
+        assert (a["run_len"] <= a["solid"]).all() and (a["lead"] <= a["run_len"]).all() and (a["trail"] <= a["run_len"]).all()
+        return int(a["slots"].sum()), int(a["solid"].sum())
+
+    reps = []
+    with okm.KmerCounter(k) as c:
+        for rep in range(repeats):
+            c.reset()
+            c.add_device_batch(dbuf.address, len(batch))
+            distinct = c.count()
+            c.set_timing(True)
+            r = {}
+            for which in ("pending", "dense"):
+                if which == "dense":
+                    c.result_device()
+                r[f"mask_{which}_ms"], r[f"stage2_{which}_ms"] = event_ms(c, ("solid_mask", "solid_runs"), runs)
+                r[f"depth_{which}_ms"], = event_ms(c, ("read_depths",), depth)
+                slots, solid = check()
+            reps.append(r)
+            log(json.dumps(r))
+    for b in (dbuf, runs_buf, depth_buf):
+        b.free()
+
+    def med(name):
+        return sorted(r[name] for r in reps)[len(reps) // 2]
+
+    def side(which):
+        m, s2, d = med(f"mask_{which}_ms"), med(f"stage2_{which}_ms"), med(f"depth_{which}_ms")
+        return {"solid_mask_ms": round(m, 4), "solid_runs_ms": round(s2, 4), "total_ms": round(m + s2, 4),
+                "read_depths_ms": round(d, 4), "ratio_to_read_depths": round((m + s2) / d, 4),
+                "stage2_share": round(s2 / (m + s2), 4)}
+
+    pend = side("pending")
+    out = {"metric": "per-read solid runs of the C2 batch against its own pending table (k=31, min_count=2) on one "
+                     "MI355X, HIP-event ms", "value": pend["total_ms"], "unit": "ms", "n_gpus": 1, "steps": steps,
+           "warmup": args.warmup, "higher_is_better": False, "dtype": "u64 keys, u32 staged counts",
+           "data": "synthetic (BASELINE configs[1] reads, device-resident)",
+           "config": {"workload": f"solid_runs: {nreads} reads ({len(batch) - nreads} bases) counted, then their solid "
+                                  "runs and their depths taken from the same device batch", "k": k,
+                      "min_count": min_count, "slots": slots, "solid": solid, "distinct": int(distinct),
+                      "repeats": repeats},
+           "pending": pend, "dense": side("dense"), "repeats": reps}
+    with open(os.path.join(ROOT, "profiles", "solid_runs.jsonl"), "a") as f:
+        f.write(json.dumps(out) + "\n")
+    return out
+
+
 def ont_batch(gbases: float, seed: int = 4):
     """ONT-like reads (okm.workloads.c4_reads): lognormal
     lengths (median 2,891, sigma 1.085, 200..100k), either strand, 5 %
@@ -1189,7 +1274,7 @@ def wl_classify(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth", "compare", "combine"],
+    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth", "compare", "combine", "solid_runs"],
                     required=True)
     ap.add_argument("--no-ref", action="store_true", help="c3: skip the one-GPU reference table")
     ap.add_argument("--c3-reads", type=int, default=C3_READS,
@@ -1214,7 +1299,7 @@ def main():
     c5 = wl_c5_dist if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.loopback else wl_c5
     out = {"query": wl_query, "build": wl_build, "wide": wl_wide, "classify": wl_classify,
            "c5": c5, "c3": wl_c3_loop, "histogram": wl_histogram, "lookup": wl_lookup, "depth": wl_depth,
-           "compare": wl_compare, "combine": wl_combine}[args.workload](args)
+           "compare": wl_compare, "combine": wl_combine, "solid_runs": wl_solid_runs}[args.workload](args)
     if out is not None:
         print(json.dumps(out), flush=True)
 
