@@ -16,6 +16,7 @@
 #include <time.h>
 #include <unistd.h>
 
+#include <initializer_list>
 #include <string>
 #include <thread>
 #include <vector>
@@ -397,20 +398,23 @@ static int read_lookup_file(const std::string &path, uint8_t k, LookupList &out)
     return rc;
 }
 
-// The reader of the --depth reads, closed on every way out of run_count.
-struct DepthReader {
+// The reader of the --depth or the --solid-runs reads, closed on every way out
+// of run_count.
+struct ReadsReader {
     okm_reader *r = nullptr;
-    ~DepthReader() {
+    ~ReadsReader() {
         if (r) okm_reader_close(r);
     }
 };
 
-// --depth: every batch of the reader through okm_group_read_depths, one line
-// per record in input order: id, windows, present, solid, sum, min, max.
-static int write_depths(okm_group *grp, okm_reader *r, const std::string &path, const std::string &out_path,
-                        uint64_t min_count) {
+// --depth and --solid-runs: every batch of the reader through `call` (false:
+// the engine failed), one line per record in input order: the id, then the
+// row's `fields`.  `doing` and `what` name the rows in the two messages.
+template <typename ROW, typename CALL>
+static int write_read_rows(okm_reader *r, const std::string &path, const std::string &out_path, CALL call,
+                           std::initializer_list<uint64_t ROW::*> fields, const char *doing, const char *what) {
     std::string lines;
-    std::vector<okm_read_depth> rows;
+    std::vector<ROW> rows;
     for (;;) {
         const uint8_t *seq, *ids;
         const uint64_t *off, *ioff;
@@ -420,53 +424,19 @@ static int write_depths(okm_group *grp, okm_reader *r, const std::string &path, 
         if (n == 0) break;
         okm_reader_ids(r, &ids, &ioff);
         rows.resize(n);
-        if (okm_group_read_depths(grp, seq, off, n, 1, min_count, rows.data()) != OKM_OK)
-            return die("GPU engine failure while taking read depths: " + err_detail());
+        if (!call(seq, off, n, rows.data()))
+            return die(std::string("GPU engine failure while ") + doing + ": " + err_detail());
         for (uint64_t i = 0; i < n; ++i) {
             lines.append(reinterpret_cast<const char *>(ids + ioff[i]), ioff[i + 1] - ioff[i]);
-            const okm_read_depth &d = rows[i];
-            for (uint64_t v : {d.windows, d.present, d.solid, d.sum, d.min, d.max}) {
+            for (const auto f : fields) {
                 lines += '\t';
-                lines += std::to_string(v);
+                lines += std::to_string(rows[i].*f);
             }
             lines += '\n';
         }
     }
     if (okm_write_file(out_path.c_str(), reinterpret_cast<const uint8_t *>(lines.data()), lines.size()) != OKM_OK)
-        return die("Failed to get output writer for depth output file: " + dbg_path(out_path));
-    return 0;
-}
-
-// --solid-runs: every batch of the reader through okm_read_solid_runs on the
-// one GPU's table, one line per record in input order: id, slots, solid,
-// run_start, run_len, lead, trail.
-static int write_solid_runs(okm_ctx *ctx, okm_reader *r, const std::string &path, const std::string &out_path,
-                            uint64_t min_count) {
-    std::string lines;
-    std::vector<okm_solid_run> rows;
-    for (;;) {
-        const uint8_t *seq, *ids;
-        const uint64_t *off, *ioff;
-        uint64_t n;
-        if (okm_reader_next(r, 128ull << 20, &seq, &off, &n) != OKM_OK)
-            return die("Error reading record from " + path);
-        if (n == 0) break;
-        okm_reader_ids(r, &ids, &ioff);
-        rows.resize(n);
-        if (!ctx || okm_read_solid_runs(ctx, seq, off, n, 1, min_count, rows.data()) != OKM_OK)
-            return die("GPU engine failure while finding solid runs: " + err_detail());
-        for (uint64_t i = 0; i < n; ++i) {
-            lines.append(reinterpret_cast<const char *>(ids + ioff[i]), ioff[i + 1] - ioff[i]);
-            const okm_solid_run &d = rows[i];
-            for (uint64_t v : {d.slots, d.solid, d.run_start, d.run_len, d.lead, d.trail}) {
-                lines += '\t';
-                lines += std::to_string(v);
-            }
-            lines += '\n';
-        }
-    }
-    if (okm_write_file(out_path.c_str(), reinterpret_cast<const uint8_t *>(lines.data()), lines.size()) != OKM_OK)
-        return die("Failed to get output writer for solid runs output file: " + dbg_path(out_path));
+        return die(std::string("Failed to get output writer for ") + what + " output file: " + dbg_path(out_path));
     return 0;
 }
 
@@ -646,13 +616,13 @@ static int run_count(const Args &a) {
     // the depth reads are opened before the engine starts (count's reader:
     // its normalisation and extension decompression, ids kept) and read in
     // batches once the table is counted
-    DepthReader depth_reader;
+    ReadsReader depth_reader;
     if (want_depth) {
         const okm_status ds = okm_reader_open2(&depth_reader.r, depth_path.c_str(), 1, OKM_READ_IDS);
         if (ds == OKM_E_IO) return die("Failed to get input reader for depth file: " + dbg_path(depth_path));
         if (ds != OKM_OK) return die("Failed to parse FASTA/Q content from depth file: " + dbg_path(depth_path));
     }
-    DepthReader solid_reader;  // the --solid-runs reads, opened as the depth reads are
+    ReadsReader solid_reader;  // the --solid-runs reads, opened as the depth reads are
     if (want_sr) {
         const okm_status ds = okm_reader_open2(&solid_reader.r, sr_path.c_str(), 1, OKM_READ_IDS);
         if (ds == OKM_E_IO) return die("Failed to get input reader for solid runs file: " + dbg_path(sr_path));
@@ -702,12 +672,27 @@ static int run_count(const Args &a) {
         phase("lookup");
     }
     if (want_depth) {  // the reads go straight to their rows; the table stays as it lies
-        if ((rc = write_depths(grp, depth_reader.r, depth_path, depth_out, depth_min))) return rc;
+        typedef okm_read_depth D;  // through the group: okm_group_read_depths
+        const auto call = [&](const uint8_t *seq, const uint64_t *off, uint64_t n, D *rows) {
+            return okm_group_read_depths(grp, seq, off, n, 1, depth_min, rows) == OKM_OK;
+        };
+        if ((rc = write_read_rows<D>(depth_reader.r, depth_path, depth_out, call,
+                                     {&D::windows, &D::present, &D::solid, &D::sum, &D::min, &D::max},
+                                     "taking read depths", "depth")))
+            return rc;
         info("orion_kmer::commands::count", "Successfully wrote the read depths to " + dbg_path(depth_out));
         phase("depth");
     }
     if (want_sr) {  // the reads go to two bit planes and those to the rows; the table stays as it lies
-        if ((rc = write_solid_runs(okm_group_owner(grp, 0), solid_reader.r, sr_path, sr_out, sr_min))) return rc;
+        typedef okm_solid_run R;  // on the one GPU's table: okm_read_solid_runs
+        okm_ctx *ctx = okm_group_owner(grp, 0);
+        const auto call = [&](const uint8_t *seq, const uint64_t *off, uint64_t n, R *rows) {
+            return ctx && okm_read_solid_runs(ctx, seq, off, n, 1, sr_min, rows) == OKM_OK;
+        };
+        if ((rc = write_read_rows<R>(solid_reader.r, sr_path, sr_out, call,
+                                     {&R::slots, &R::solid, &R::run_start, &R::run_len, &R::lead, &R::trail},
+                                     "finding solid runs", "solid runs")))
+            return rc;
         info("orion_kmer::commands::count", "Successfully wrote the solid runs to " + dbg_path(sr_out));
         phase("solid runs");
     }

@@ -5,9 +5,9 @@
 // present windows' counts.
 //
 // One kernel goes from the batch bytes to the rows: no key array is written
-// and nothing of the table is gathered.  A thread owns kDepthSeg consecutive
-// window starts.  It builds the 2-bit codes and the valid mask once
-// (okm_scan.h, count's normalisation), then takes the windows kDepthFly at a
+// and nothing of the table is gathered.  A thread owns kScanSeg consecutive
+// window starts (the read-batch scan, okm_read_scan.h).  It builds the 2-bit
+// codes and the valid mask once, then takes the windows kDepthFly at a
 // time (one: see there): their canonical keys from the codes, their searches
 // level by level with the loads of all of them in flight together
 // (search_last_le, okm_search.h), and their counts added to six register
@@ -23,9 +23,9 @@
 // round at the end of the launch sequence: min = present ? ~field : 0.
 #include <hip/hip_runtime.h>
 
-#include "okm_depth_keys.h"
 #include "okm_dev_common.h"
 #include "okm_internal.h"
+#include "okm_read_scan.h"
 #include "okm_scan.h"
 #include "okm_search.h"
 
@@ -38,13 +38,6 @@ namespace okm {
 #define OKM_DEPTH_WAVE 1
 #endif
 
-constexpr int kDepthBlock = 256;
-// Window starts per thread: the loads of okm_scan.h come in 16-byte words
-// (window starts + a 32 or 64 byte halo), so 16 is the smallest run; a longer
-// one only adds loaded words to carry (24 at k > 32 already).
-constexpr int kDepthSeg = 16;
-static_assert(kDepthSeg == kKeySeg, "DepthKeys (okm_depth_keys.h) is built for this run");
-constexpr int kDepthTile = kDepthBlock * kDepthSeg;  // 4096 bytes per workgroup
 // Searches a lane keeps in flight.  One, as in the lookup (okm_lookup.hip
 // kLookFly): the kernel is bound by the memory system's rate of random 64-byte
 // reads, which the waves of a CU already fill, and a search in flight holds
@@ -53,7 +46,7 @@ constexpr int kDepthTile = kDepthBlock * kDepthSeg;  // 4096 bytes per workgroup
 // measured 77.5 / 79.0 / 81.5 / 96.0 ms and 97.5 / 104.3 / 111.3 / 110.7 ms
 // (profiles/AB_LOG.md).
 constexpr int kDepthFly = OKM_DEPTH_FLY;
-static_assert(kDepthSeg % kDepthFly == 0, "whole groups of searches");
+static_assert(kScanSeg % kDepthFly == 0, "whole groups of searches");
 constexpr int kRowWords = 6;  // okm_read_depth: windows, present, solid, sum, min, max
 static_assert(sizeof(okm_read_depth) == kRowWords * sizeof(ull), "rows are six u64");
 
@@ -62,28 +55,20 @@ __device__ __forceinline__ uint32_t depth_sep_bytes(uint32_t w) {  // separator 
     return __popc(zero_bytes(x));
 }
 
-__device__ __forceinline__ uint32_t depth_sep_mask(const uint32_t *w) {  // bit j: byte j is a separator
-    uint32_t m = 0;
-#pragma unroll
-    for (int i = 0; i < kDepthSeg; ++i)
-        m |= (((w[i >> 2] >> ((i & 3) * 8)) & 0xFFu) == OKM_RECORD_SEPARATOR ? 1u : 0u) << i;
-    return m;
-}
-
 // tile_cnt[t] = separators among the bytes of tile t (bytes at or past n: none)
-__global__ __launch_bounds__(kDepthBlock) void k_depth_sep_count(const uint8_t *__restrict__ seq, uint64_t n,
-                                                                 ull *__restrict__ tile_cnt) {
-    __shared__ ull wsum[kDepthBlock / 64];
-    const uint64_t w0 = (uint64_t)blockIdx.x * kDepthTile + (uint64_t)threadIdx.x * kDepthSeg;
+__global__ __launch_bounds__(kScanBlock) void k_depth_sep_count(const uint8_t *__restrict__ seq, uint64_t n,
+                                                                ull *__restrict__ tile_cnt) {
+    __shared__ ull wsum[kScanBlock / 64];
+    const uint64_t w0 = (uint64_t)blockIdx.x * kScanTile + (uint64_t)threadIdx.x * kScanSeg;
     uint32_t c = 0;
-    if (w0 + kDepthSeg <= n) {
+    if (w0 + kScanSeg <= n) {
         const uint4 v = *reinterpret_cast<const uint4 *>(seq + w0);
         c = depth_sep_bytes(v.x) + depth_sep_bytes(v.y) + depth_sep_bytes(v.z) + depth_sep_bytes(v.w);
     } else {
         for (uint64_t i = w0; i < n; ++i) c += seq[i] == OKM_RECORD_SEPARATOR;
     }
     ull tot;
-    block_excl_scan<kDepthBlock>((ull)c, wsum, &tot);
+    block_excl_scan<kScanBlock>((ull)c, wsum, &tot);
     if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
 }
 
@@ -109,26 +94,26 @@ __device__ __forceinline__ void depth_flush(ull *__restrict__ rows, uint64_t nre
 }
 
 template <typename KT, typename TAB, bool WIN>
-__global__ __launch_bounds__(kDepthBlock) void k_read_depths(const uint8_t *__restrict__ seq, uint64_t n,
-                                                             const ull *__restrict__ tile_pre, TAB tab, uint32_t k,
-                                                             ull min_count, ull *__restrict__ rows, uint64_t nrec) {
+__global__ __launch_bounds__(kScanBlock) void k_read_depths(const uint8_t *__restrict__ seq, uint64_t n,
+                                                            const ull *__restrict__ tile_pre, TAB tab, uint32_t k,
+                                                            ull min_count, ull *__restrict__ rows, uint64_t nrec) {
     typedef KeyOps<KT> O;
-    typedef DepthKeys<KT> DK;
-    __shared__ ull wsum[kDepthBlock / 64];
-    const uint64_t w0 = (uint64_t)blockIdx.x * kDepthTile + (uint64_t)threadIdx.x * kDepthSeg;
-    WinWords<kDepthSeg, DK::kHalo> ww;
-    load_windows<kDepthSeg, DK::kHalo>(seq, n, w0, ww);  // bytes at or past n read as 0: no base, no separator
-    const uint32_t sepm = depth_sep_mask(ww.w);
+    typedef ScanKeys<KT> SK;
+    __shared__ ull wsum[kScanBlock / 64];
+    const uint64_t w0 = (uint64_t)blockIdx.x * kScanTile + (uint64_t)threadIdx.x * kScanSeg;
+    typename SK::Words ww;
+    load_windows<kScanSeg, SK::kHalo>(seq, n, w0, ww);  // bytes at or past n read as 0: no base, no separator
+    const uint32_t sepm = sep_mask_bytes(ww.w);
     ull tot;
-    ull rec = tile_pre[blockIdx.x] + block_excl_scan<kDepthBlock>((ull)__popc(sepm), wsum, &tot);
+    ull rec = tile_pre[blockIdx.x] + block_excl_scan<kScanBlock>((ull)__popc(sepm), wsum, &tot);
     // (no thread leaves early: the wave reduction below needs every lane)
-    Codes<DK::kNP> c;
-    make_codes<DK::kNP, false>(ww.w, c);  // count's validity: either case, U reads as T
-    const uint32_t vmask = DK::valid_mask(c, k);
+    typename SK::Coded c;
+    make_codes<SK::kNP, false>(ww.w, c);  // count's validity: either case, U reads as T
+    const uint32_t vmask = SK::valid_mask(c, k);
     tab.begin();
     DepthAcc acc = {0, 0, 0, 0, 0, 0};
 #pragma unroll
-    for (int g = 0; g < kDepthSeg / kDepthFly; ++g) {
+    for (int g = 0; g < kScanSeg / kDepthFly; ++g) {
         KT q[kDepthFly];
         bool live[kDepthFly], hit[kDepthFly];
         ull cnt[kDepthFly];
@@ -136,7 +121,7 @@ __global__ __launch_bounds__(kDepthBlock) void k_read_depths(const uint8_t *__re
         for (int f = 0; f < kDepthFly; ++f) {
             const int j = g * kDepthFly + f;
             live[f] = (vmask >> j) & 1u;
-            q[f] = live[f] ? DK::key(c, j, k) : O::empty();
+            q[f] = live[f] ? SK::key(c, j, k) : O::empty();
         }
         tab.find(q, live, cnt, hit);
 #pragma unroll
@@ -186,35 +171,7 @@ __global__ __launch_bounds__(256) void k_depth_fix(ull *__restrict__ rows, uint6
     r[4] = r[1] ? ~r[4] : 0ull;
 }
 
-uint64_t depth_tiles(uint64_t n_bytes) { return (n_bytes + kDepthTile - 1) / kDepthTile; }
-
-template <typename KT, typename TAB>
-static void launch_depth_tab(hipStream_t s, uint32_t ntiles, const uint8_t *seq, uint64_t n, const ull *pre,
-                             const TAB &tab, uint32_t k, uint64_t min_count, bool count_windows, ull *rows,
-                             uint64_t nrec) {
-    if (count_windows)
-        hipLaunchKernelGGL((k_read_depths<KT, TAB, true>), dim3(ntiles), dim3(kDepthBlock), 0, s, seq, n, pre, tab, k,
-                           (ull)min_count, rows, nrec);
-    else
-        hipLaunchKernelGGL((k_read_depths<KT, TAB, false>), dim3(ntiles), dim3(kDepthBlock), 0, s, seq, n, pre, tab, k,
-                           (ull)min_count, rows, nrec);
-}
-
-template <typename KT>
-static void launch_depth_key(hipStream_t s, uint32_t ntiles, const uint8_t *seq, uint64_t n, const ull *pre,
-                             const TableView &t, uint32_t k, uint64_t min_count, bool count_windows, ull *rows,
-                             uint64_t nrec) {
-    if (!t.runs) {
-        const FindDense<KT, kDepthFly> tab{reinterpret_cast<const KT *>(t.keys), t.counts, t.n};
-        launch_depth_tab<KT>(s, ntiles, seq, n, pre, tab, k, min_count, count_windows, rows, nrec);
-    } else if (t.narrow) {
-        const FindItems<KT, true, kDepthFly> tab{reinterpret_cast<const KT *>(t.first), t.desc, t.n_desc, t.counts, 0};
-        launch_depth_tab<KT>(s, ntiles, seq, n, pre, tab, k, min_count, count_windows, rows, nrec);
-    } else {
-        const FindItems<KT, false, kDepthFly> tab{reinterpret_cast<const KT *>(t.first), t.desc, t.n_desc, t.counts, 0};
-        launch_depth_tab<KT>(s, ntiles, seq, n, pre, tab, k, min_count, count_windows, rows, nrec);
-    }
-}
+uint64_t depth_tiles(uint64_t n_bytes) { return (n_bytes + kScanTile - 1) / kScanTile; }
 
 void launch_read_depths(void *stream, const uint8_t *seq, uint64_t n, uint64_t nrec, uint32_t k, bool wide,
                         const TableView &t, uint64_t min_count, bool count_windows, unsigned long long *tiles,
@@ -223,13 +180,19 @@ void launch_read_depths(void *stream, const uint8_t *seq, uint64_t n, uint64_t n
     hipStream_t s = (hipStream_t)stream;
     const uint64_t nt = depth_tiles(n);  // < 2^31 (the caller's check)
     ull *cnt = tiles, *pre = cnt + nt, *scr = pre + nt;
-    hipLaunchKernelGGL(k_depth_sep_count, dim3((uint32_t)nt), dim3(kDepthBlock), 0, s, seq, n, cnt);
+    hipLaunchKernelGGL(k_depth_sep_count, dim3((uint32_t)nt), dim3(kScanBlock), 0, s, seq, n, cnt);
     launch_exclusive_scan(stream, cnt, pre, nt, scr);
     ull *r = reinterpret_cast<ull *>(rows);
-    if (wide)
-        launch_depth_key<K128>(s, (uint32_t)nt, seq, n, pre, t, k, min_count, count_windows, r, nrec);
-    else
-        launch_depth_key<ull>(s, (uint32_t)nt, seq, n, pre, t, k, min_count, count_windows, r, nrec);
+    with_finder<kDepthFly>(t, wide, [&](const auto &tab) {
+        typedef std::decay_t<decltype(tab)> TAB;
+        typedef typename TAB::Key KT;
+        if (count_windows)
+            hipLaunchKernelGGL((k_read_depths<KT, TAB, true>), dim3((uint32_t)nt), dim3(kScanBlock), 0, s, seq, n, pre,
+                               tab, k, (ull)min_count, r, nrec);
+        else
+            hipLaunchKernelGGL((k_read_depths<KT, TAB, false>), dim3((uint32_t)nt), dim3(kScanBlock), 0, s, seq, n, pre,
+                               tab, k, (ull)min_count, r, nrec);
+    });
 }
 
 void launch_read_depths_fix(void *stream, okm_read_depth *rows, uint64_t nrec) {

@@ -3872,133 +3872,132 @@ okm_status okm_combine_counts(okm_ctx *a, okm_ctx *b, okm_combine_op op, uint64_
     return OKM_OK;
 }
 
-// Per-record depths of reads against the table, searched as okm_lookup_counts
-// searches it (TableForm::Search).  One launch sequence per (slice, batch):
-//   [launch_lookup_index, the first time]  k_depth_sep_count  scan
-//   k_read_depths  [k_depth_fix, after the batch's last slice]
-// An empty table still takes one scan, which counts the windows.
-// A device batch keeps its rows in the caller's array across the slices.  Host
-// records go up in chunks of whole records (kDepthChunk bytes, at least one
-// record) through scratch sized for the largest chunk; with several slices
-// every slice scans every chunk again and the chunk's rows are combined on the
-// host (depth_combine), so the table goes up once whatever the input's size.
+// The two per-record readers of read batches, okm_read_depths[_device] and
+// okm_read_solid_runs[_device]: both search the table as okm_lookup_counts
+// searches it (TableForm::Search), batch by batch.  A batch is the caller's
+// device batch, or one chunk of host records: whole records, kDepthChunk bytes
+// (at least one record), packed and sent up through scratch sized for the
+// largest chunk.  ReadCall is what the four entry points share; how slices
+// and chunks nest is each reader's own (see there).
 constexpr uint64_t kDepthChunk = uint64_t(32) << 20;
 
+extern "C++" {  // (templates)
 namespace {
-struct DepthCall {
+// What the entry points check alike, in this order, then the count.  Host
+// records (offsets) need seq where any record has bytes.  Without records
+// nothing is touched: OKM_OK, and the caller returns.
+okm_status read_enter(okm_ctx *c, const std::string &fn, bool null_arg, bool too_large, const char *too_large_msg,
+                      uint64_t n_records, const uint8_t *seq, const uint64_t *offsets) {
+    if (!c || null_arg) return fail(OKM_E_ARG, fn + ": null argument");
+    if (too_large) return fail(OKM_E_ARG, fn + ": " + too_large_msg);
+    if (c->mode == OKM_MODE_SET) return fail(OKM_E_STATE, fn + ": a set-mode context has no counts");
+    if (n_records == 0) return OKM_OK;
+    if (offsets && offsets[n_records] != offsets[0] && !seq) return fail(OKM_E_ARG, fn + ": null seq");
+    HIP_TRY(hipSetDevice(c->device));
+    return okm_count(c, nullptr);
+}
+
+template <typename ROW>
+struct ReadCall {
     okm_ctx *c;
     Blocks scratch;
     TableReader tab;
-    uint64_t nslices;  // scans per batch
-    unsigned long long *tiles = nullptr;
-    explicit DepthCall(okm_ctx *ctx)
-        : c(ctx), scratch(*ctx->pool), tab(ctx, TableForm::Search), nslices(std::max<uint64_t>(tab.nslices, 1)) {}
-    // the table's side of the scratch, and the tile words of a batch of at most max_bytes
-    okm_status prepare(uint64_t max_bytes) {
-        OKM_TRY(tab.prepare(scratch));
-        const uint64_t nt = depth_tiles(max_bytes);
-        OKM_TRY(scratch.get(2 * nt + scan_tmp_elems(nt) + 1, &tiles));
-        return OKM_OK;
-    }
-    // slice si's scan of one device batch into rows (zeroed before its slice 0)
-    okm_status scan(uint64_t si, const uint8_t *d_seq, uint64_t nb, uint64_t nrec, uint64_t min_count,
-                    okm_read_depth *rows, bool fix) {
-        c->timer.begin(c->stream);
-        tab.index(c->stream, si);
-        launch_read_depths(c->stream, d_seq, nb, nrec, c->k, c->wide, tab.view(si), min_count, si == 0, tiles, rows);
-        if (fix) launch_read_depths_fix(c->stream, rows, nrec);
-        // the read bytes in and the rows out, once per batch however many slices scan it
-        c->timer.end(c->stream, "read_depths", si == 0 ? (double)nb + 48.0 * (double)nrec : 0.0);
-        HIP_TRY(hipGetLastError());
-        return OKM_OK;
-    }
-};
-}  // namespace
-
-okm_status okm_read_depths_device(okm_ctx *c, const uint8_t *d_seq, uint64_t n_bytes, uint64_t n_records,
-                                  uint64_t min_count, okm_read_depth *d_out) {
-    if (!c || (n_records && (!d_out || (!d_seq && n_bytes))))
-        return fail(OKM_E_ARG, "okm_read_depths_device: null argument");
-    if (n_bytes >> 42 || n_records >> 40) return fail(OKM_E_ARG, "okm_read_depths_device: batch too large");
-    if (c->mode == OKM_MODE_SET) return fail(OKM_E_STATE, "okm_read_depths_device: a set-mode context has no counts");
-    if (n_records == 0) return OKM_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    OKM_TRY(okm_count(c, nullptr));
-    DepthCall d(c);
-    const uint8_t *src = d_seq;
-    if (n_bytes) {
-        OKM_TRY(d.prepare(n_bytes));
-        if ((reinterpret_cast<uintptr_t>(d_seq) & 15u) != 0) {  // the scan loads 16-B words
-            uint64_t *copy = nullptr;
-            OKM_TRY(d.scratch.get(n_bytes / 8 + 1, &copy));
-            HIP_TRY(hipMemcpyAsync(copy, d_seq, n_bytes, hipMemcpyDeviceToDevice, c->stream));
-            src = reinterpret_cast<const uint8_t *>(copy);
-        }
-    }
-    HIP_TRY(hipMemsetAsync(d_out, 0, n_records * sizeof(okm_read_depth), c->stream));
-    for (uint64_t si = 0; n_bytes && si < d.nslices; ++si) {
-        OKM_TRY(d.tab.upload(c->stream, si));
-        OKM_TRY(d.scan(si, src, n_bytes, n_records, min_count, d_out, si + 1 == d.nslices));
-    }
-    OKM_TRY(sync(c));
-    d.scratch.free_all();
-    return OKM_OK;
-}
-
-okm_status okm_read_depths(okm_ctx *c, const uint8_t *seq, const uint64_t *offsets, uint64_t n_records, int normalized,
-                           uint64_t min_count, okm_read_depth *out) {
-    if (!c || (n_records && (!offsets || !out))) return fail(OKM_E_ARG, "okm_read_depths: null argument");
-    if (n_records >> 40) return fail(OKM_E_ARG, "okm_read_depths: more than 2^40 records");
-    if (c->mode == OKM_MODE_SET) return fail(OKM_E_STATE, "okm_read_depths: a set-mode context has no counts");
-    if (n_records == 0) return OKM_OK;
-    if (offsets[n_records] != offsets[0] && !seq) return fail(OKM_E_ARG, "okm_read_depths: null seq");
-    HIP_TRY(hipSetDevice(c->device));
-    OKM_TRY(okm_count(c, nullptr));
-    // chunks of whole records: [first record, one past the last)
-    uint64_t chunk = kDepthChunk;
-    if (const int64_t e = test_knob(OKM_TEST_DEPTH_CHUNK); e > 0) chunk = (uint64_t)e;
+    uint64_t nslices;  // searches per batch: an empty table still takes one
+    unsigned long long *tiles = nullptr, *planes = nullptr;  // the reader's kernels' words for one batch
+    // host records: the chunks [first record, one past the last) and what one chunk goes through
     std::vector<std::pair<uint64_t, uint64_t>> chunks;
     uint64_t max_bytes = 0, max_recs = 0;
-    for (uint64_t r0 = 0; r0 < n_records;) {
-        uint64_t r1 = r0 + 1;  // at least one record, whatever its size
-        const auto bytes = [&](uint64_t e) { return offsets[e] - offsets[r0] + (e - r0); };
-        while (r1 < n_records && bytes(r1 + 1) <= chunk) ++r1;
-        if (bytes(r1) >> 42) return fail(OKM_E_ARG, "okm_read_depths: record too large");
-        chunks.emplace_back(r0, r1);
-        max_bytes = std::max(max_bytes, bytes(r1));
-        max_recs = std::max(max_recs, r1 - r0);
-        r0 = r1;
-    }
-    DepthCall d(c);
-    OKM_TRY(d.prepare(max_bytes));
     uint64_t *dseq = nullptr;
-    okm_read_depth *drows = nullptr;
-    OKM_TRY(d.scratch.get(max_bytes / 8 + 1, &dseq));
-    OKM_TRY(d.scratch.get(max_recs, &drows));
-    std::vector<uint8_t> packed(max_bytes);
-    std::vector<okm_read_depth> part(d.nslices > 1 ? max_recs : 0);
-    for (uint64_t si = 0; si < d.nslices; ++si) {
-        OKM_TRY(d.tab.upload(c->stream, si));
-        for (const auto &ch : chunks) {
-            const uint64_t r0 = ch.first, nr = ch.second - ch.first;
-            const uint64_t nb = pack_records(packed.data(), seq, offsets, r0, ch.second, normalized);
-            HIP_TRY(hipMemcpyAsync(dseq, packed.data(), nb, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemsetAsync(drows, 0, nr * sizeof(okm_read_depth), c->stream));
-            OKM_TRY(d.scan(si, reinterpret_cast<const uint8_t *>(dseq), nb, nr, min_count, drows, true));
-            okm_read_depth *dst = si == 0 ? out + r0 : part.data();
-            HIP_TRY(hipMemcpyAsync(dst, drows, nr * sizeof(okm_read_depth), hipMemcpyDeviceToHost, c->stream));
-            OKM_TRY(sync(c));  // `packed` and `part` are reused
-            if (si)
-                for (uint64_t i = 0; i < nr; ++i) depth_combine(out[r0 + i], part[i]);
-        }
+    ROW *drows = nullptr;
+    std::vector<uint8_t> packed;
+    explicit ReadCall(okm_ctx *ctx)
+        : c(ctx), scratch(*ctx->pool), tab(ctx, TableForm::Search), nslices(std::max<uint64_t>(tab.nslices, 1)) {}
+    // the table's side of the scratch, then the reader's own for a batch
+    okm_status prepare(uint64_t plane_words, uint64_t tile_words) {
+        OKM_TRY(tab.prepare(scratch));
+        if (plane_words) OKM_TRY(scratch.get(plane_words, &planes));
+        OKM_TRY(scratch.get(tile_words, &tiles));
+        return OKM_OK;
     }
-    d.scratch.free_all();
+    // *src = the device batch where the scan can read it: it loads 16-B words
+    okm_status aligned(const uint8_t *d_seq, uint64_t n_bytes, const uint8_t **src) {
+        *src = d_seq;
+        if ((reinterpret_cast<uintptr_t>(d_seq) & 15u) == 0) return OKM_OK;
+        uint64_t *copy = nullptr;
+        OKM_TRY(scratch.get(n_bytes / 8 + 1, &copy));
+        HIP_TRY(hipMemcpyAsync(copy, d_seq, n_bytes, hipMemcpyDeviceToDevice, c->stream));
+        *src = reinterpret_cast<const uint8_t *>(copy);
+        return OKM_OK;
+    }
+    // Cuts the records into chunks; one of 2^byte_bits bytes or more (a single record then) is `too_large`.
+    okm_status cut(const uint64_t *offsets, uint64_t n_records, int byte_bits, const char *too_large) {
+        uint64_t chunk = kDepthChunk;
+        if (const int64_t e = test_knob(OKM_TEST_DEPTH_CHUNK); e > 0) chunk = (uint64_t)e;  // tests: several chunks
+        for (uint64_t r0 = 0; r0 < n_records;) {
+            uint64_t r1 = r0 + 1;  // at least one record, whatever its size
+            const auto bytes = [&](uint64_t e) { return offsets[e] - offsets[r0] + (e - r0); };
+            while (r1 < n_records && bytes(r1 + 1) <= chunk) ++r1;
+            if (bytes(r1) >> byte_bits) return fail(OKM_E_ARG, too_large);
+            chunks.emplace_back(r0, r1);
+            max_bytes = std::max(max_bytes, bytes(r1));
+            max_recs = std::max(max_recs, r1 - r0);
+            r0 = r1;
+        }
+        return OKM_OK;
+    }
+    // the largest chunk's bytes and rows, on the device and packed on the host
+    okm_status stage() {
+        OKM_TRY(scratch.get(max_bytes / 8 + 1, &dseq));
+        OKM_TRY(scratch.get(max_recs, &drows));
+        packed.resize(max_bytes);
+        return OKM_OK;
+    }
+    const uint8_t *batch() const { return reinterpret_cast<const uint8_t *>(dseq); }
+    // Every chunk in turn: packed, sent up to batch(), then run(first record,
+    // records, bytes), which ends with download(): its sync frees `packed`.
+    template <typename RUN>
+    okm_status each_chunk(const uint8_t *seq, const uint64_t *offsets, int normalized, RUN run) {
+        for (const auto &ch : chunks) {
+            const uint64_t nb = pack_records(packed.data(), seq, offsets, ch.first, ch.second, normalized);
+            HIP_TRY(hipMemcpyAsync(dseq, packed.data(), nb, hipMemcpyHostToDevice, c->stream));
+            OKM_TRY(run(ch.first, ch.second - ch.first, nb));
+        }
+        return OKM_OK;
+    }
+    okm_status download(ROW *dst, uint64_t nr) {
+        HIP_TRY(hipMemcpyAsync(dst, drows, nr * sizeof(ROW), hipMemcpyDeviceToHost, c->stream));
+        return sync(c);
+    }
+};
+
+// Depth.  One launch sequence per (slice, batch):
+//   [launch_lookup_index, the first time]  k_depth_sep_count  scan
+//   k_read_depths  [k_depth_fix, after the batch's last slice]
+// An empty table still takes one scan, which counts the windows.
+// A device batch keeps its rows in the caller's array across the slices.
+// With host records the slice loop is the OUTER one: every slice scans every
+// chunk again and the chunk's rows are combined on the host (depth_combine),
+// so the table goes up once whatever the input's size.
+typedef ReadCall<okm_read_depth> DepthCall;
+okm_status depth_prepare(DepthCall &d, uint64_t max_bytes) {
+    const uint64_t nt = depth_tiles(max_bytes);
+    return d.prepare(0, 2 * nt + scan_tmp_elems(nt) + 1);
+}
+// slice si's scan of one device batch into rows (zeroed before its slice 0)
+okm_status depth_scan(DepthCall &d, uint64_t si, const uint8_t *d_seq, uint64_t nb, uint64_t nrec, uint64_t min_count,
+                      okm_read_depth *rows, bool fix) {
+    okm_ctx *c = d.c;
+    c->timer.begin(c->stream);
+    d.tab.index(c->stream, si);
+    launch_read_depths(c->stream, d_seq, nb, nrec, c->k, c->wide, d.tab.view(si), min_count, si == 0, d.tiles, rows);
+    if (fix) launch_read_depths_fix(c->stream, rows, nrec);
+    // the read bytes in and the rows out, once per batch however many slices scan it
+    c->timer.end(c->stream, "read_depths", si == 0 ? (double)nb + 48.0 * (double)nrec : 0.0);
+    HIP_TRY(hipGetLastError());
     return OKM_OK;
 }
 
-// Per-record solid runs of reads against the table, searched as the depth
-// reader searches it.  Per batch (a device batch, or one chunk of host
-// records, cut as okm_read_depths cuts them):
+// Solid runs.  Per batch:
 //   for every slice:  [launch_lookup_index, the first time]  k_solid_mask
 //   then once:        k_runs_init  k_runs_tiles  scan  k_runs_carry  k_runs_rows  k_runs_fix
 // The slices of a host-resident table meet in the solid bit plane (OR), not in
@@ -4010,66 +4009,92 @@ okm_status okm_read_depths(okm_ctx *c, const uint8_t *seq, const uint64_t *offse
 // searched where it lies.  (Keeping every chunk's planes, n / 4 bytes in all,
 // would let the table go up once; it would also make the call's footprint
 // grow with its input, which the chunking is there to prevent.)
-namespace {
-struct SolidCall {
-    okm_ctx *c;
-    Blocks scratch;
-    TableReader tab;
-    uint64_t nslices;  // searches per batch
-    unsigned long long *planes = nullptr, *tiles = nullptr;
-    explicit SolidCall(okm_ctx *ctx)
-        : c(ctx), scratch(*ctx->pool), tab(ctx, TableForm::Search), nslices(std::max<uint64_t>(tab.nslices, 1)) {}
-    // the table's side of the scratch, the bit planes and the tile words of a batch of at most max_bytes
-    okm_status prepare(uint64_t max_bytes) {
-        OKM_TRY(tab.prepare(scratch));
-        const uint64_t nt = solid_tiles(max_bytes);
-        OKM_TRY(scratch.get(2 * solid_plane_words(max_bytes), &planes));
-        OKM_TRY(scratch.get(4 * nt + scan_tmp_elems(nt) + 1, &tiles));
-        return OKM_OK;
-    }
-    // one device batch against every slice, into rows (device; every row is written)
-    okm_status batch(const uint8_t *d_seq, uint64_t nb, uint64_t nrec, uint64_t min_count, okm_solid_run *rows) {
-        for (uint64_t si = 0; si < nslices; ++si) {
-            OKM_TRY(tab.upload(c->stream, si));
-            c->timer.begin(c->stream);
-            tab.index(c->stream, si);
-            launch_solid_mask(c->stream, d_seq, nb, c->k, c->wide, tab.view(si), min_count, si == 0, planes);
-            // the read bytes in and the rows out, once per batch however many slices search it
-            c->timer.end(c->stream, "solid_mask", si == 0 ? (double)nb + 48.0 * (double)nrec : 0.0);
-        }
+typedef ReadCall<okm_solid_run> SolidCall;
+okm_status solid_prepare(SolidCall &d, uint64_t max_bytes) {
+    const uint64_t nt = solid_tiles(max_bytes);
+    return d.prepare(2 * solid_plane_words(max_bytes), 4 * nt + scan_tmp_elems(nt) + 1);
+}
+// one device batch against every slice, into rows (device; every row is written)
+okm_status solid_batch(SolidCall &d, const uint8_t *d_seq, uint64_t nb, uint64_t nrec, uint64_t min_count,
+                       okm_solid_run *rows) {
+    okm_ctx *c = d.c;
+    for (uint64_t si = 0; si < d.nslices; ++si) {
+        OKM_TRY(d.tab.upload(c->stream, si));
         c->timer.begin(c->stream);
-        launch_solid_runs(c->stream, nb, nrec, c->k, planes, tiles, rows);
-        c->timer.end(c->stream, "solid_runs", 16.0 * (double)solid_plane_words(nb) + 48.0 * (double)nrec);
-        HIP_TRY(hipGetLastError());
-        return OKM_OK;
+        d.tab.index(c->stream, si);
+        launch_solid_mask(c->stream, d_seq, nb, c->k, c->wide, d.tab.view(si), min_count, si == 0, d.planes);
+        // the read bytes in and the rows out, once per batch however many slices search it
+        c->timer.end(c->stream, "solid_mask", si == 0 ? (double)nb + 48.0 * (double)nrec : 0.0);
     }
-};
+    c->timer.begin(c->stream);
+    launch_solid_runs(c->stream, nb, nrec, c->k, d.planes, d.tiles, rows);
+    c->timer.end(c->stream, "solid_runs", 16.0 * (double)solid_plane_words(nb) + 48.0 * (double)nrec);
+    HIP_TRY(hipGetLastError());
+    return OKM_OK;
+}
 }  // namespace
+}  // extern "C++"
+
+okm_status okm_read_depths_device(okm_ctx *c, const uint8_t *d_seq, uint64_t n_bytes, uint64_t n_records,
+                                  uint64_t min_count, okm_read_depth *d_out) {
+    OKM_TRY(read_enter(c, "okm_read_depths_device", n_records && (!d_out || (!d_seq && n_bytes)),
+                       n_bytes >> 42 || n_records >> 40, "batch too large", n_records, nullptr, nullptr));
+    if (n_records == 0) return OKM_OK;
+    DepthCall d(c);
+    const uint8_t *src = d_seq;
+    if (n_bytes) {
+        OKM_TRY(depth_prepare(d, n_bytes));
+        OKM_TRY(d.aligned(d_seq, n_bytes, &src));
+    }
+    HIP_TRY(hipMemsetAsync(d_out, 0, n_records * sizeof(okm_read_depth), c->stream));
+    for (uint64_t si = 0; n_bytes && si < d.nslices; ++si) {
+        OKM_TRY(d.tab.upload(c->stream, si));
+        OKM_TRY(depth_scan(d, si, src, n_bytes, n_records, min_count, d_out, si + 1 == d.nslices));
+    }
+    OKM_TRY(sync(c));
+    d.scratch.free_all();
+    return OKM_OK;
+}
+
+okm_status okm_read_depths(okm_ctx *c, const uint8_t *seq, const uint64_t *offsets, uint64_t n_records, int normalized,
+                           uint64_t min_count, okm_read_depth *out) {
+    OKM_TRY(read_enter(c, "okm_read_depths", n_records && (!offsets || !out), n_records >> 40,
+                       "more than 2^40 records", n_records, seq, offsets));
+    if (n_records == 0) return OKM_OK;
+    DepthCall d(c);
+    OKM_TRY(d.cut(offsets, n_records, 42, "okm_read_depths: record too large"));
+    OKM_TRY(depth_prepare(d, d.max_bytes));
+    OKM_TRY(d.stage());
+    std::vector<okm_read_depth> part(d.nslices > 1 ? d.max_recs : 0);
+    for (uint64_t si = 0; si < d.nslices; ++si) {
+        OKM_TRY(d.tab.upload(c->stream, si));
+        OKM_TRY(d.each_chunk(seq, offsets, normalized, [&](uint64_t r0, uint64_t nr, uint64_t nb) {
+            HIP_TRY(hipMemsetAsync(d.drows, 0, nr * sizeof(okm_read_depth), c->stream));
+            OKM_TRY(depth_scan(d, si, d.batch(), nb, nr, min_count, d.drows, true));
+            OKM_TRY(d.download(si == 0 ? out + r0 : part.data(), nr));  // (`part` is reused too)
+            if (si)
+                for (uint64_t i = 0; i < nr; ++i) depth_combine(out[r0 + i], part[i]);
+            return OKM_OK;
+        }));
+    }
+    d.scratch.free_all();
+    return OKM_OK;
+}
 
 okm_status okm_read_solid_runs_device(okm_ctx *c, const uint8_t *d_seq, uint64_t n_bytes, uint64_t n_records,
                                       uint64_t min_count, okm_solid_run *d_out) {
-    if (!c || (n_records && (!d_out || (!d_seq && n_bytes))))
-        return fail(OKM_E_ARG, "okm_read_solid_runs_device: null argument");
-    if (n_bytes >> 32 || n_records >> 40) return fail(OKM_E_ARG, "okm_read_solid_runs_device: batch too large");
-    if (c->mode == OKM_MODE_SET)
-        return fail(OKM_E_STATE, "okm_read_solid_runs_device: a set-mode context has no counts");
+    OKM_TRY(read_enter(c, "okm_read_solid_runs_device", n_records && (!d_out || (!d_seq && n_bytes)),
+                       n_bytes >> 32 || n_records >> 40, "batch too large", n_records, nullptr, nullptr));
     if (n_records == 0) return OKM_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    OKM_TRY(okm_count(c, nullptr));
     if (n_bytes == 0) {  // records, all of them empty
         HIP_TRY(hipMemsetAsync(d_out, 0, n_records * sizeof(okm_solid_run), c->stream));
         return sync(c);
     }
     SolidCall d(c);
-    OKM_TRY(d.prepare(n_bytes));
-    const uint8_t *src = d_seq;
-    if ((reinterpret_cast<uintptr_t>(d_seq) & 15u) != 0) {  // the scan loads 16-B words
-        uint64_t *copy = nullptr;
-        OKM_TRY(d.scratch.get(n_bytes / 8 + 1, &copy));
-        HIP_TRY(hipMemcpyAsync(copy, d_seq, n_bytes, hipMemcpyDeviceToDevice, c->stream));
-        src = reinterpret_cast<const uint8_t *>(copy);
-    }
-    OKM_TRY(d.batch(src, n_bytes, n_records, min_count, d_out));
+    OKM_TRY(solid_prepare(d, n_bytes));
+    const uint8_t *src;
+    OKM_TRY(d.aligned(d_seq, n_bytes, &src));
+    OKM_TRY(solid_batch(d, src, n_bytes, n_records, min_count, d_out));
     OKM_TRY(sync(c));
     d.scratch.free_all();
     return OKM_OK;
@@ -4077,43 +4102,17 @@ okm_status okm_read_solid_runs_device(okm_ctx *c, const uint8_t *d_seq, uint64_t
 
 okm_status okm_read_solid_runs(okm_ctx *c, const uint8_t *seq, const uint64_t *offsets, uint64_t n_records,
                                int normalized, uint64_t min_count, okm_solid_run *out) {
-    if (!c || (n_records && (!offsets || !out))) return fail(OKM_E_ARG, "okm_read_solid_runs: null argument");
-    if (n_records >> 40) return fail(OKM_E_ARG, "okm_read_solid_runs: more than 2^40 records");
-    if (c->mode == OKM_MODE_SET) return fail(OKM_E_STATE, "okm_read_solid_runs: a set-mode context has no counts");
+    OKM_TRY(read_enter(c, "okm_read_solid_runs", n_records && (!offsets || !out), n_records >> 40,
+                       "more than 2^40 records", n_records, seq, offsets));
     if (n_records == 0) return OKM_OK;
-    if (offsets[n_records] != offsets[0] && !seq) return fail(OKM_E_ARG, "okm_read_solid_runs: null seq");
-    HIP_TRY(hipSetDevice(c->device));
-    OKM_TRY(okm_count(c, nullptr));
-    // chunks of whole records, as okm_read_depths cuts them: [first record, one past the last)
-    uint64_t chunk = kDepthChunk;
-    if (const int64_t e = test_knob(OKM_TEST_DEPTH_CHUNK); e > 0) chunk = (uint64_t)e;
-    std::vector<std::pair<uint64_t, uint64_t>> chunks;
-    uint64_t max_bytes = 0, max_recs = 0;
-    for (uint64_t r0 = 0; r0 < n_records;) {
-        uint64_t r1 = r0 + 1;  // at least one record, whatever its size
-        const auto bytes = [&](uint64_t e) { return offsets[e] - offsets[r0] + (e - r0); };
-        while (r1 < n_records && bytes(r1 + 1) <= chunk) ++r1;
-        if (bytes(r1) >> 32) return fail(OKM_E_ARG, "okm_read_solid_runs: batch too large (one record of 2^32 bytes)");
-        chunks.emplace_back(r0, r1);
-        max_bytes = std::max(max_bytes, bytes(r1));
-        max_recs = std::max(max_recs, r1 - r0);
-        r0 = r1;
-    }
     SolidCall d(c);
-    OKM_TRY(d.prepare(max_bytes));
-    uint64_t *dseq = nullptr;
-    okm_solid_run *drows = nullptr;
-    OKM_TRY(d.scratch.get(max_bytes / 8 + 1, &dseq));
-    OKM_TRY(d.scratch.get(max_recs, &drows));
-    std::vector<uint8_t> packed(max_bytes);
-    for (const auto &ch : chunks) {
-        const uint64_t r0 = ch.first, nr = ch.second - ch.first;
-        const uint64_t nb = pack_records(packed.data(), seq, offsets, r0, ch.second, normalized);
-        HIP_TRY(hipMemcpyAsync(dseq, packed.data(), nb, hipMemcpyHostToDevice, c->stream));
-        OKM_TRY(d.batch(reinterpret_cast<const uint8_t *>(dseq), nb, nr, min_count, drows));
-        HIP_TRY(hipMemcpyAsync(out + r0, drows, nr * sizeof(okm_solid_run), hipMemcpyDeviceToHost, c->stream));
-        OKM_TRY(sync(c));  // `packed` is reused
-    }
+    OKM_TRY(d.cut(offsets, n_records, 32, "okm_read_solid_runs: batch too large (one record of 2^32 bytes)"));
+    OKM_TRY(solid_prepare(d, d.max_bytes));
+    OKM_TRY(d.stage());
+    OKM_TRY(d.each_chunk(seq, offsets, normalized, [&](uint64_t r0, uint64_t nr, uint64_t nb) {
+        OKM_TRY(solid_batch(d, d.batch(), nb, nr, min_count, d.drows));
+        return d.download(out + r0, nr);
+    }));
     d.scratch.free_all();
     return OKM_OK;
 }

@@ -427,8 +427,8 @@ void launch_combine_write(void *stream, const TableView &d, const TableView &s, 
 // Per-record k-mer depth (okm_depth.hip): one scan of a device batch (records
 // joined by separators, 16-byte aligned, n bytes) against one representation
 // of the table; rows[r] accumulates record r's okm_read_depth (r = separators
-// before the window, rows past nrec dropped).  The table is searched as the
-// lookup searches it, flat or through a pending table's run list.
+// before the window, rows past nrec dropped).  The table is searched through
+// the view's finder (okm_search.h with_finder).
 // Rows start zeroed; any number of launches (slices of a host-resident table)
 // add into them, exactly one of them with count_windows; the min field holds
 // the largest ~count until launch_read_depths_fix turns it round, once, after
@@ -454,8 +454,8 @@ inline void depth_combine(okm_read_depth &a, const okm_read_depth &b) {
 // Per-record solid runs (okm_solid.hip), in two stages over a device batch
 // (records joined by separators, 16-byte aligned, 0 < n < 2^32 bytes).
 // planes: 2 * solid_plane_words(n) words, the solid bit plane and then the
-// separator bit plane, one bit per batch byte.  launch_solid_mask searches one
-// representation of the table as launch_read_depths does: the batch's first
+// separator bit plane, one bit per batch byte.  launch_solid_mask is
+// launch_read_depths' scan and search into bits: the batch's first
 // launch (`first`) writes both planes whole, every later one (a further slice
 // of a host-resident table) ORs its hits into the solid plane.
 // launch_solid_runs then turns the planes into rows[nrec] (r = separators

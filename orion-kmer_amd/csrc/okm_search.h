@@ -1,7 +1,8 @@
 // okm_search.h — the search every in-place reader of a counted table shares
 // (okm_lookup.hip, okm_depth.hip, okm_compare.hip), and the two finders built
 // on it: FindDense and FindItems, one per form of a TableView
-// (okm_internal.h), used by the lookup and the depth kernels.
+// (okm_internal.h), used by the lookup, the depth and the solid kernels;
+// with_finder picks the one that reads a view.
 //
 // Every representation of the table is sorted by key, so a lookup is a search,
 // and all of them use one routine, search_last_le: the position of the last
@@ -84,6 +85,7 @@ __device__ __forceinline__ K128 load_query<K128>(const ull *queries, ull i) {
 // table, nothing is read)
 template <typename KT, int QF>
 struct FindDense {
+    typedef KT Key;
     const KT *keys;
     const uint64_t *counts;
     ull n;
@@ -113,6 +115,7 @@ struct FindDense {
 // count lies at the same position; NARROW: the runs' counts are u32.
 template <typename KT, bool NARROW, int QF>
 struct FindItems {
+    typedef KT Key;
     const KT *first;
     const LookItem *desc;
     const ull *n_desc;
@@ -153,5 +156,25 @@ struct FindItems {
         }
     }
 };
+
+// f(tab), tab the finder that reads view t: its Key by `wide`, its form by the
+// view's, FLY searches in flight.  (Host side: f launches a kernel with it.)
+template <typename KT, int FLY, typename F>
+inline void with_finder_of(const TableView &t, F f) {
+    const KT *first = reinterpret_cast<const KT *>(t.first);
+    if (!t.runs)
+        f(FindDense<KT, FLY>{reinterpret_cast<const KT *>(t.keys), t.counts, t.n});
+    else if (t.narrow)
+        f(FindItems<KT, true, FLY>{first, t.desc, t.n_desc, t.counts, 0});
+    else
+        f(FindItems<KT, false, FLY>{first, t.desc, t.n_desc, t.counts, 0});
+}
+template <int FLY, typename F>
+inline void with_finder(const TableView &t, bool wide, F f) {
+    if (wide)
+        with_finder_of<K128, FLY>(t, f);
+    else
+        with_finder_of<ull, FLY>(t, f);
+}
 
 }  // namespace okm

@@ -8,9 +8,9 @@
 // invalid.  So over the whole batch the solid bits form one bit string whose
 // maximal runs of ones each belong to one record, and the work splits in two:
 //
-// Stage 1, k_solid_mask: the search.  k_read_depths' tiling (256 threads, 16
-// window starts each, okm_scan.h's loads and codes, DepthKeys, one search in
-// flight through FindDense / FindItems), but a thread forms 16 solid bits and
+// Stage 1, k_solid_mask: the search.  The read-batch scan of okm_read_scan.h
+// (256 threads, 16 window starts each), one search in flight through
+// FindDense / FindItems, but a thread forms 16 solid bits and
 // 16 separator bits and stores them, coalesced, into two bit planes of one bit
 // per batch byte (bit p & 63 of word p >> 6).  The first launch of a batch
 // stores both planes plainly, over whole stage-2 tiles, so nothing is zeroed
@@ -49,19 +49,17 @@
 // Positions are 32 bits in the packed best: a batch holds < 2^32 bytes.
 #include <hip/hip_runtime.h>
 
-#include "okm_depth_keys.h"
 #include "okm_dev_common.h"
 #include "okm_internal.h"
+#include "okm_read_scan.h"
 #include "okm_scan.h"
 #include "okm_search.h"
 
 namespace okm {
 
-constexpr int kSolidBlock = 256;
-constexpr int kSolidTile = kSolidBlock * kKeySeg;  // 4096 bytes per stage-1 workgroup
 constexpr int kRunsBlock = 256;
 constexpr int kRunsTile = kRunsBlock * 64;         // 16384 positions per stage-2 workgroup
-static_assert(kRunsTile % kSolidTile == 0, "stage 1 fills whole stage-2 tiles");
+static_assert(kRunsTile % kScanTile == 0, "stage 1 fills whole stage-2 tiles");
 constexpr int kSolidRowWords = 6;  // okm_solid_run: slots, solid, run_start, run_len, lead, trail
 static_assert(sizeof(okm_solid_run) == kSolidRowWords * sizeof(ull), "rows are six u64");
 // Until k_runs_fix the row's words hold: 0 the record's first byte, 2 its end
@@ -75,75 +73,38 @@ uint64_t solid_plane_words(uint64_t n_bytes) { return solid_tiles(n_bytes) * kRu
 // Stage 1
 // ---------------------------------------------------------------------------
 
-// bit j: byte j of the thread's 16 is a separator (four bytes a step, as pack4 gathers its bad bits)
-__device__ __forceinline__ uint32_t solid_sep_bits(const uint32_t *w) {
-    uint32_t m = 0;
-#pragma unroll
-    for (int i = 0; i < kKeySeg / 4; ++i) {
-        const uint32_t z = zero_bytes(w[i] ^ (0x01010101u * OKM_RECORD_SEPARATOR));
-        m |= ((((z >> 7) & 0x01010101u) * 0x00204081u) >> 21 & 0xFu) << (4 * i);
-    }
-    return m;
-}
-
 // FIRST: the batch's first launch: stores both planes (zeros where there is
 // nothing); otherwise ORs this table's hits into the solid plane.
 template <typename KT, typename TAB, bool FIRST>
-__global__ __launch_bounds__(kSolidBlock) void k_solid_mask(const uint8_t *__restrict__ seq, uint64_t n, TAB tab,
-                                                            uint32_t k, ull min_count, uint16_t *__restrict__ solid,
-                                                            uint16_t *__restrict__ sep) {
+__global__ __launch_bounds__(kScanBlock) void k_solid_mask(const uint8_t *__restrict__ seq, uint64_t n, TAB tab,
+                                                           uint32_t k, ull min_count, uint16_t *__restrict__ solid,
+                                                           uint16_t *__restrict__ sep) {
     typedef KeyOps<KT> O;
-    typedef DepthKeys<KT> DK;
-    const uint64_t t = (uint64_t)blockIdx.x * kSolidBlock + threadIdx.x;  // the planes' 16-bit word of this thread
-    const uint64_t w0 = t * kKeySeg;
-    WinWords<kKeySeg, DK::kHalo> ww;
-    load_windows<kKeySeg, DK::kHalo>(seq, n, w0, ww);  // bytes at or past n read as 0: no base, no separator
-    Codes<DK::kNP> c;
-    make_codes<DK::kNP, false>(ww.w, c);  // count's validity: either case, U reads as T
-    const uint32_t vmask = DK::valid_mask(c, k);
+    typedef ScanKeys<KT> SK;
+    const uint64_t t = (uint64_t)blockIdx.x * kScanBlock + threadIdx.x;  // the planes' 16-bit word of this thread
+    const uint64_t w0 = t * kScanSeg;
+    typename SK::Words ww;
+    load_windows<kScanSeg, SK::kHalo>(seq, n, w0, ww);  // bytes at or past n read as 0: no base, no separator
+    typename SK::Coded c;
+    make_codes<SK::kNP, false>(ww.w, c);  // count's validity: either case, U reads as T
+    const uint32_t vmask = SK::valid_mask(c, k);
     tab.begin();
     uint32_t bits = 0;
 #pragma unroll
-    for (int j = 0; j < kKeySeg; ++j) {
+    for (int j = 0; j < kScanSeg; ++j) {
         KT q[1];
         bool live[1], hit[1];
         ull cnt[1];
         live[0] = (vmask >> j) & 1u;
-        q[0] = live[0] ? DK::key(c, j, k) : O::empty();
+        q[0] = live[0] ? SK::key(c, j, k) : O::empty();
         tab.find(q, live, cnt, hit);
         bits |= (hit[0] && cnt[0] >= min_count ? 1u : 0u) << j;
     }
     if (FIRST) {
         solid[t] = (uint16_t)bits;
-        sep[t] = (uint16_t)solid_sep_bits(ww.w);
+        sep[t] = (uint16_t)sep_mask_words(ww.w);
     } else if (bits) {
         solid[t] |= (uint16_t)bits;
-    }
-}
-
-template <typename KT, typename TAB>
-static void launch_mask_tab(hipStream_t s, uint32_t nblocks, const uint8_t *seq, uint64_t n, const TAB &tab,
-                            uint32_t k, uint64_t min_count, bool first, uint16_t *solid, uint16_t *sep) {
-    if (first)
-        hipLaunchKernelGGL((k_solid_mask<KT, TAB, true>), dim3(nblocks), dim3(kSolidBlock), 0, s, seq, n, tab, k,
-                           (ull)min_count, solid, sep);
-    else
-        hipLaunchKernelGGL((k_solid_mask<KT, TAB, false>), dim3(nblocks), dim3(kSolidBlock), 0, s, seq, n, tab, k,
-                           (ull)min_count, solid, sep);
-}
-
-template <typename KT>
-static void launch_mask_key(hipStream_t s, uint32_t nblocks, const uint8_t *seq, uint64_t n, const TableView &t,
-                            uint32_t k, uint64_t min_count, bool first, uint16_t *solid, uint16_t *sep) {
-    if (!t.runs) {
-        const FindDense<KT, 1> tab{reinterpret_cast<const KT *>(t.keys), t.counts, t.n};
-        launch_mask_tab<KT>(s, nblocks, seq, n, tab, k, min_count, first, solid, sep);
-    } else if (t.narrow) {
-        const FindItems<KT, true, 1> tab{reinterpret_cast<const KT *>(t.first), t.desc, t.n_desc, t.counts, 0};
-        launch_mask_tab<KT>(s, nblocks, seq, n, tab, k, min_count, first, solid, sep);
-    } else {
-        const FindItems<KT, false, 1> tab{reinterpret_cast<const KT *>(t.first), t.desc, t.n_desc, t.counts, 0};
-        launch_mask_tab<KT>(s, nblocks, seq, n, tab, k, min_count, first, solid, sep);
     }
 }
 
@@ -154,11 +115,17 @@ void launch_solid_mask(void *stream, const uint8_t *seq, uint64_t n, uint32_t k,
     uint16_t *solid = reinterpret_cast<uint16_t *>(planes), *sep = reinterpret_cast<uint16_t *>(planes + words);
     // the first launch covers the planes' every word; a later one only the batch
     const uint64_t bytes = first ? solid_tiles(n) * kRunsTile : n;
-    const uint32_t nblocks = (uint32_t)((bytes + kSolidTile - 1) / kSolidTile);  // n < 2^32
-    if (wide)
-        launch_mask_key<K128>((hipStream_t)stream, nblocks, seq, n, t, k, min_count, first, solid, sep);
-    else
-        launch_mask_key<ull>((hipStream_t)stream, nblocks, seq, n, t, k, min_count, first, solid, sep);
+    const uint32_t nblocks = (uint32_t)((bytes + kScanTile - 1) / kScanTile);  // n < 2^32
+    with_finder<1>(t, wide, [&](const auto &tab) {
+        typedef std::decay_t<decltype(tab)> TAB;
+        typedef typename TAB::Key KT;
+        if (first)
+            hipLaunchKernelGGL((k_solid_mask<KT, TAB, true>), dim3(nblocks), dim3(kScanBlock), 0, (hipStream_t)stream,
+                               seq, n, tab, k, (ull)min_count, solid, sep);
+        else
+            hipLaunchKernelGGL((k_solid_mask<KT, TAB, false>), dim3(nblocks), dim3(kScanBlock), 0, (hipStream_t)stream,
+                               seq, n, tab, k, (ull)min_count, solid, sep);
+    });
 }
 
 // ---------------------------------------------------------------------------

@@ -18,8 +18,8 @@ FIELDS = ("windows", "present", "solid", "sum", "min", "max")
 M64 = (1 << 64) - 1
 
 # the kernel's geometry
-SEG = 16              # okm_depth.hip kDepthSeg: window starts per thread
-TILE = 4096           # okm_depth.hip kDepthTile = kDepthBlock (256) * kDepthSeg: window starts per workgroup
+SEG = 16              # okm_read_scan.h kScanSeg: window starts per thread
+TILE = 4096           # okm_read_scan.h kScanTile = kScanBlock (256) * kScanSeg: window starts per workgroup
 WAVE = 64 * SEG       # the bytes of one wave: without a separator among them its rows leave as one
 CHUNK = 32 << 20      # okm_engine.hip kDepthChunk: packed bytes per uploaded chunk of host records
 

@@ -91,10 +91,10 @@ def test_combine_is_the_documented_rule():
 # ---------------------------------------------------------------------------
 
 def test_constants_mirror_the_sources():
-    src = open(os.path.join(ROOT, "orion-kmer_amd", "csrc", "okm_depth.hip")).read()
-    block = int(re.search(r"constexpr int kDepthBlock = (\d+);", src).group(1))
-    seg = int(re.search(r"constexpr int kDepthSeg = (\d+);", src).group(1))
-    assert "kDepthTile = kDepthBlock * kDepthSeg" in src
+    src = open(os.path.join(ROOT, "orion-kmer_amd", "csrc", "okm_read_scan.h")).read()
+    block = int(re.search(r"constexpr int kScanBlock = (\d+);", src).group(1))
+    seg = int(re.search(r"constexpr int kScanSeg = (\d+);", src).group(1))
+    assert "kScanTile = kScanBlock * kScanSeg" in src
     assert (seg, block * seg, 64 * seg) == (dc.SEG, dc.TILE, dc.WAVE)
     eng = open(os.path.join(ROOT, "orion-kmer_amd", "csrc", "okm_engine.hip")).read()
     assert int(re.search(r"kDepthChunk = uint64_t\((\d+)\) << 20;", eng).group(1)) << 20 == dc.CHUNK
