@@ -280,6 +280,56 @@ okm_status okm_read_solid_runs(okm_ctx *ctx, const uint8_t *seq, const uint64_t 
 okm_status okm_read_solid_runs_device(okm_ctx *ctx, const uint8_t *d_seq, uint64_t n_bytes, uint64_t n_records,
                                       uint64_t min_count, okm_solid_run *d_out /* device, n_records */);
 
+/* Per-record count quantiles: the median k-mer count of each record, and more
+ * generally a percentile of its counts -- what khmer normalize-by-median and
+ * filter-abund -V decide by, what BBNorm normalises by, and the robust
+ * per-read coverage estimate (sum / windows is pulled up by repeats and down
+ * by every sequencing error, which costs k windows); an extension, the
+ * reference has none.  Row r is out[r * (1 + nq) ..]:
+ *   word 0       windows, okm_read_depth's `windows` by definition
+ *   word 1 + i   quantile q[i]: the counts of the record's valid windows, an
+ *                absent k-mer counting 0, sorted ascending; the element at
+ *                index min(floor(windows * num / den), windows - 1); 0 when
+ *                windows == 0
+ * so 1/2 is khmer's counts[n / 2], 0/1 the read's shallowest window and 1/1
+ * its deepest.  Every count is clipped to OKM_QUANTILE_COUNT_MAX before it is
+ * ranked; clipping is monotone, so it commutes with the order statistic and
+ * each value is EXACTLY min(true quantile, 2^32 - 2): a definition, not an
+ * approximation.  The rows are found on the device from a plane of one 32-bit
+ * word per batch byte, by exact radix selection per record; the read bytes are
+ * searched once and the table stays where and as it lies, as for
+ * okm_read_depths.
+ * There is no group form: quantiles taken against owners of disjoint key
+ * ranges do not combine by any rule on the rows (the median of a read is not a
+ * function of its medians over parts of the table), only in the owners' count
+ * planes, which never leave the device. */
+#define OKM_MAX_QUANTILES 4
+#define OKM_QUANTILE_COUNT_MAX 0xFFFFFFFEull
+typedef struct okm_quantile {
+    uint32_t num, den;  /* the fraction num / den: 0 <= num <= den, den > 0 */
+} okm_quantile;
+/* Everything else as okm_read_solid_runs: the record layout and `normalized`,
+ * every record gets a row (zeros when it is empty or shorter than k), counts
+ * first if batches are pending, read-only on the table in every
+ * representation, host records go up in chunks of whole records.  An empty
+ * table: windows as they are, zeros elsewhere.  n_records == 0: OK, nothing
+ * touched.  A set-mode context has no counts: OKM_E_STATE.  One chunk -- so in
+ * effect one record -- of 2^32 bytes or more: OKM_E_ARG.  nq == 0, nq >
+ * OKM_MAX_QUANTILES, a quantile with den == 0 or num > den: OKM_E_ARG. */
+okm_status okm_read_count_quantiles(okm_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, uint64_t n_records,
+                                    int normalized, const okm_quantile *q, uint32_t nq,
+                                    uint64_t *out /* host, n_records * (1 + nq) */);
+/* The same over a device batch, as okm_read_solid_runs_device takes it (a
+ * record's index is the number of separators before it, records past
+ * n_records are dropped and rows past the last record are zero, an
+ * unterminated last record is taken as it stands, bytes at and beyond n_bytes
+ * are never looked at).  q is host memory.  n_bytes >= 2^32: OKM_E_ARG (batch
+ * too large); no device memory for the batch's plane (4 bytes per batch byte):
+ * OKM_E_NOMEM, the context as it was. */
+okm_status okm_read_count_quantiles_device(okm_ctx *ctx, const uint8_t *d_seq, uint64_t n_bytes, uint64_t n_records,
+                                           const okm_quantile *q /* host */, uint32_t nq,
+                                           uint64_t *d_out /* device, n_records * (1 + nq) */);
+
 /* Two counted tables compared: the keys both hold, with their counts -- what
  * `kmc_tools simple intersect` with counters_min, or two jellyfish tables,
  * answer; an extension, the reference's compare works on keys alone.  An entry

@@ -220,7 +220,7 @@ static const char *kVersion = "orion-kmer 0.1.0";
 
 static void print_help(const std::string &cmd) {
     if (cmd == "count")
-        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n      --depth <FASTX>              Take the k-mer depth of every record of FASTX in the whole table (extension)\n      --depth-output <FILE>        Where --depth writes id<TAB>windows<TAB>present<TAB>solid<TAB>sum<TAB>min<TAB>max, in input order\n      --depth-min-count <N>        A window is solid when its k-mer's count is at least N [default: 2]\n      --solid-runs <FASTX>         Find the solid runs of every record of FASTX in the whole table: where its solid k-mers lie (extension)\n      --solid-runs-output <FILE>   Where --solid-runs writes id<TAB>slots<TAB>solid<TAB>run_start<TAB>run_len<TAB>lead<TAB>trail, in input order\n      --solid-runs-min-count <N>   A slot is solid when its k-mer's count is at least N [default: 2]\n      --compare <FASTX>            Count FASTX as a second table (same k) and compare the two tables with their counts (extension)\n      --compare-output <FILE>      Where --compare writes field<TAB>value: the shared k-mers, their counts, Jaccard, weighted Jaccard, Bray-Curtis\n      --compare-min-count <N>      Minimum count of a k-mer of the --compare table (--min-count: of the first table) [default: 1]\n      --combine <FASTX>            Count FASTX as a second table (same k) and combine the two tables into a third (extension)\n      --combine-op <OP>            union, intersect, intersect_left, difference or subtract (the first table is the left one)\n      --combine-output <FILE>      Where --combine writes the combined table as KMER<TAB>COUNT lines\n      --combine-min-count <N>      Minimum count of a k-mer of the --combine table (--min-count: of the first table) [default: 1]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
+        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n      --depth <FASTX>              Take the k-mer depth of every record of FASTX in the whole table (extension)\n      --depth-output <FILE>        Where --depth writes id<TAB>windows<TAB>present<TAB>solid<TAB>sum<TAB>min<TAB>max, in input order\n      --depth-min-count <N>        A window is solid when its k-mer's count is at least N [default: 2]\n      --solid-runs <FASTX>         Find the solid runs of every record of FASTX in the whole table: where its solid k-mers lie (extension)\n      --solid-runs-output <FILE>   Where --solid-runs writes id<TAB>slots<TAB>solid<TAB>run_start<TAB>run_len<TAB>lead<TAB>trail, in input order\n      --solid-runs-min-count <N>   A slot is solid when its k-mer's count is at least N [default: 2]\n      --quantiles <FASTX>          Per record of FASTX: quantiles of its k-mers' counts in the table, the median by default (extension)\n      --quantiles-output <FILE>    Where --quantiles writes id<TAB>windows<TAB>one value per quantile, in input order\n      --quantiles-at <A/B,...>     Up to 4 fractions: the sorted counts' element at index windows * A / B [default: 1/2]\n      --compare <FASTX>           Count FASTX as a second table (same k) and compare the two tables with their counts (extension)\n      --compare-output <FILE>      Where --compare writes field<TAB>value: the shared k-mers, their counts, Jaccard, weighted Jaccard, Bray-Curtis\n      --compare-min-count <N>      Minimum count of a k-mer of the --compare table (--min-count: of the first table) [default: 1]\n      --combine <FASTX>            Count FASTX as a second table (same k) and combine the two tables into a third (extension)\n      --combine-op <OP>            union, intersect, intersect_left, difference or subtract (the first table is the left one)\n      --combine-output <FILE>      Where --combine writes the combined table as KMER<TAB>COUNT lines\n      --combine-min-count <N>      Minimum count of a k-mer of the --combine table (--min-count: of the first table) [default: 1]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
     else if (cmd == "build")
         printf("Build a unique k-mer database from genome assemblies\n\nUsage: orion-kmer build [OPTIONS] --kmer-size <KMER_SIZE> --genomes <GENOME_FILES>... --output-file <OUTPUT_FILE>\n");
     else if (cmd == "compare")
@@ -398,7 +398,24 @@ static int read_lookup_file(const std::string &path, uint8_t k, LookupList &out)
     return rc;
 }
 
-// The reader of the --depth or the --solid-runs reads, closed on every way out
+// --quantiles-at: 1 to OKM_MAX_QUANTILES fractions A/B joined by commas, each
+// of two decimal numbers with 0 <= A <= B, 0 < B < 2^32.
+static bool parse_quantiles(const std::string &s, std::vector<okm_quantile> &out) {
+    out.clear();
+    for (size_t at = 0; at <= s.size();) {
+        const size_t end = std::min(s.find(',', at), s.size()), slash = s.find('/', at);
+        uint64_t num, den;
+        if (slash >= end || !parse_u64(s.substr(at, slash - at), num) ||
+            !parse_u64(s.substr(slash + 1, end - slash - 1), den) || den == 0 || den >> 32 || num > den ||
+            out.size() == OKM_MAX_QUANTILES)
+            return false;
+        out.push_back({(uint32_t)num, (uint32_t)den});
+        at = end + 1;
+    }
+    return true;
+}
+
+// The reader of the --depth, --solid-runs or --quantiles reads, closed on every way out
 // of run_count.
 struct ReadsReader {
     okm_reader *r = nullptr;
@@ -407,14 +424,16 @@ struct ReadsReader {
     }
 };
 
-// --depth and --solid-runs: every batch of the reader through `call` (false:
-// the engine failed), one line per record in input order: the id, then the
-// row's `fields`.  `doing` and `what` name the rows in the two messages.
-template <typename ROW, typename CALL>
-static int write_read_rows(okm_reader *r, const std::string &path, const std::string &out_path, CALL call,
-                           std::initializer_list<uint64_t ROW::*> fields, const char *doing, const char *what) {
+// --depth, --solid-runs and --quantiles: every batch of the reader through
+// `call` (false: the engine failed), one line per record in input order: the
+// id, then the `width` words of the record's row (the C ABI's row structs are
+// that many uint64_t in the order they are printed).  `doing` and `what` name
+// the rows in the two messages.
+template <typename CALL>
+static int write_read_rows(okm_reader *r, const std::string &path, const std::string &out_path, size_t width, CALL call,
+                           const char *doing, const char *what) {
     std::string lines;
-    std::vector<ROW> rows;
+    std::vector<uint64_t> rows;
     for (;;) {
         const uint8_t *seq, *ids;
         const uint64_t *off, *ioff;
@@ -423,14 +442,14 @@ static int write_read_rows(okm_reader *r, const std::string &path, const std::st
             return die("Error reading record from " + path);
         if (n == 0) break;
         okm_reader_ids(r, &ids, &ioff);
-        rows.resize(n);
+        rows.resize(n * width);
         if (!call(seq, off, n, rows.data()))
             return die(std::string("GPU engine failure while ") + doing + ": " + err_detail());
         for (uint64_t i = 0; i < n; ++i) {
             lines.append(reinterpret_cast<const char *>(ids + ioff[i]), ioff[i + 1] - ioff[i]);
-            for (const auto f : fields) {
+            for (size_t f = 0; f < width; ++f) {
                 lines += '\t';
-                lines += std::to_string(rows[i].*f);
+                lines += std::to_string(rows[i * width + f]);
             }
             lines += '\n';
         }
@@ -558,6 +577,22 @@ static int run_count(const Args &a) {
         return usage_error("invalid value '" + srm + "' for '--solid-runs-min-count <N>'");
     if (want_sr && g_gpus != 1)
         return usage_error("the argument '--solid-runs <FASTX>' cannot be used with '--gpus <GPUS>' other than 1");
+    // --quantiles <FASTX> --quantiles-output <FILE> [--quantiles-at A/B[,A/B
+    // ...]]: per record of FASTX, quantiles of its windows' counts in the WHOLE
+    // table, the median (1/2) by default (what khmer normalize-by-median and
+    // BBNorm decide by; an extension); the two flags need one another and the
+    // at flag needs them.  One GPU only: the owners' rows do not combine.
+    std::string qt_path, qt_out, qta;
+    const bool want_qt = get_one(a, "quantiles", qt_path), has_qtout = get_one(a, "quantiles-output", qt_out);
+    const bool has_qtat = get_one(a, "quantiles-at", qta);
+    if (want_qt != has_qtout || (has_qtat && !want_qt))
+        return usage_error(std::string("the following required arguments were not provided:\n  ") +
+                           (want_qt ? "--quantiles-output <FILE>" : "--quantiles <FASTX>"));
+    std::vector<okm_quantile> qt_at{{1, 2}};
+    if (has_qtat && !parse_quantiles(qta, qt_at))
+        return usage_error("invalid value '" + qta + "' for '--quantiles-at <A/B,...>'");
+    if (want_qt && g_gpus != 1)
+        return usage_error("the argument '--quantiles <FASTX>' cannot be used with '--gpus <GPUS>' other than 1");
     // --compare <FASTX> --compare-output <FILE> [--compare-min-count <N>]: FASTX
     // is counted at the same k into a second table and the two tables are
     // compared with their counts (kmc_tools intersect with counters_min; an
@@ -628,6 +663,12 @@ static int run_count(const Args &a) {
         if (ds == OKM_E_IO) return die("Failed to get input reader for solid runs file: " + dbg_path(sr_path));
         if (ds != OKM_OK) return die("Failed to parse FASTA/Q content from solid runs file: " + dbg_path(sr_path));
     }
+    ReadsReader quant_reader;  // the --quantiles reads, likewise
+    if (want_qt) {
+        const okm_status ds = okm_reader_open2(&quant_reader.r, qt_path.c_str(), 1, OKM_READ_IDS);
+        if (ds == OKM_E_IO) return die("Failed to get input reader for quantiles file: " + dbg_path(qt_path));
+        if (ds != OKM_OK) return die("Failed to parse FASTA/Q content from quantiles file: " + dbg_path(qt_path));
+    }
     // one table across all inputs (count.rs:48), on g_gpus GPUs (default 1),
     // started while the first input is parsed
     phase("start");
@@ -673,12 +714,11 @@ static int run_count(const Args &a) {
     }
     if (want_depth) {  // the reads go straight to their rows; the table stays as it lies
         typedef okm_read_depth D;  // through the group: okm_group_read_depths
-        const auto call = [&](const uint8_t *seq, const uint64_t *off, uint64_t n, D *rows) {
-            return okm_group_read_depths(grp, seq, off, n, 1, depth_min, rows) == OKM_OK;
+        static_assert(sizeof(D) == 6 * sizeof(uint64_t), "windows, present, solid, sum, min, max");
+        const auto call = [&](const uint8_t *seq, const uint64_t *off, uint64_t n, uint64_t *rows) {
+            return okm_group_read_depths(grp, seq, off, n, 1, depth_min, reinterpret_cast<D *>(rows)) == OKM_OK;
         };
-        if ((rc = write_read_rows<D>(depth_reader.r, depth_path, depth_out, call,
-                                     {&D::windows, &D::present, &D::solid, &D::sum, &D::min, &D::max},
-                                     "taking read depths", "depth")))
+        if ((rc = write_read_rows(depth_reader.r, depth_path, depth_out, 6, call, "taking read depths", "depth")))
             return rc;
         info("orion_kmer::commands::count", "Successfully wrote the read depths to " + dbg_path(depth_out));
         phase("depth");
@@ -686,15 +726,26 @@ static int run_count(const Args &a) {
     if (want_sr) {  // the reads go to two bit planes and those to the rows; the table stays as it lies
         typedef okm_solid_run R;  // on the one GPU's table: okm_read_solid_runs
         okm_ctx *ctx = okm_group_owner(grp, 0);
-        const auto call = [&](const uint8_t *seq, const uint64_t *off, uint64_t n, R *rows) {
-            return ctx && okm_read_solid_runs(ctx, seq, off, n, 1, sr_min, rows) == OKM_OK;
+        static_assert(sizeof(R) == 6 * sizeof(uint64_t), "slots, solid, run_start, run_len, lead, trail");
+        const auto call = [&](const uint8_t *seq, const uint64_t *off, uint64_t n, uint64_t *rows) {
+            return ctx && okm_read_solid_runs(ctx, seq, off, n, 1, sr_min, reinterpret_cast<R *>(rows)) == OKM_OK;
         };
-        if ((rc = write_read_rows<R>(solid_reader.r, sr_path, sr_out, call,
-                                     {&R::slots, &R::solid, &R::run_start, &R::run_len, &R::lead, &R::trail},
-                                     "finding solid runs", "solid runs")))
+        if ((rc = write_read_rows(solid_reader.r, sr_path, sr_out, 6, call, "finding solid runs", "solid runs")))
             return rc;
         info("orion_kmer::commands::count", "Successfully wrote the solid runs to " + dbg_path(sr_out));
         phase("solid runs");
+    }
+    if (want_qt) {  // the reads go to a count plane and that to the rows; the table stays as it lies
+        okm_ctx *ctx = okm_group_owner(grp, 0);  // on the one GPU's table: okm_read_count_quantiles
+        const auto call = [&](const uint8_t *seq, const uint64_t *off, uint64_t n, uint64_t *rows) {
+            return ctx && okm_read_count_quantiles(ctx, seq, off, n, 1, qt_at.data(), (uint32_t)qt_at.size(), rows) ==
+                              OKM_OK;
+        };
+        if ((rc = write_read_rows(quant_reader.r, qt_path, qt_out, 1 + qt_at.size(), call, "taking count quantiles",
+                                  "quantiles")))
+            return rc;
+        info("orion_kmer::commands::count", "Successfully wrote the count quantiles to " + dbg_path(qt_out));
+        phase("quantiles");
     }
     if (want_cmp) {  // both tables are merged as their counts left them
         if ((rc = write_compare(okm_group_owner(grp, 0), k, wide, cmp_path, cmp_out, min_count, cmp_min))) return rc;
@@ -1262,6 +1313,9 @@ int main(int argc, char **argv) {
         spec.push_back({"solid-runs", 0, true, false});
         spec.push_back({"solid-runs-output", 0, true, false});
         spec.push_back({"solid-runs-min-count", 0, true, false});
+        spec.push_back({"quantiles", 0, true, false});
+        spec.push_back({"quantiles-output", 0, true, false});
+        spec.push_back({"quantiles-at", 0, true, false});
         spec.push_back({"compare", 0, true, false});
         spec.push_back({"compare-output", 0, true, false});
         spec.push_back({"compare-min-count", 0, true, false});

@@ -173,6 +173,11 @@ __global__ __launch_bounds__(256) void k_depth_fix(ull *__restrict__ rows, uint6
 
 uint64_t depth_tiles(uint64_t n_bytes) { return (n_bytes + kScanTile - 1) / kScanTile; }
 
+void launch_depth_sep_count(void *stream, const uint8_t *seq, uint64_t n, unsigned long long *tile_cnt) {
+    hipLaunchKernelGGL(k_depth_sep_count, dim3((uint32_t)depth_tiles(n)), dim3(kScanBlock), 0, (hipStream_t)stream, seq,
+                       n, tile_cnt);
+}
+
 void launch_read_depths(void *stream, const uint8_t *seq, uint64_t n, uint64_t nrec, uint32_t k, bool wide,
                         const TableView &t, uint64_t min_count, bool count_windows, unsigned long long *tiles,
                         okm_read_depth *rows) {
@@ -180,7 +185,7 @@ void launch_read_depths(void *stream, const uint8_t *seq, uint64_t n, uint64_t n
     hipStream_t s = (hipStream_t)stream;
     const uint64_t nt = depth_tiles(n);  // < 2^31 (the caller's check)
     ull *cnt = tiles, *pre = cnt + nt, *scr = pre + nt;
-    hipLaunchKernelGGL(k_depth_sep_count, dim3((uint32_t)nt), dim3(kScanBlock), 0, s, seq, n, cnt);
+    launch_depth_sep_count(stream, seq, n, cnt);
     launch_exclusive_scan(stream, cnt, pre, nt, scr);
     ull *r = reinterpret_cast<ull *>(rows);
     with_finder<kDepthFly>(t, wide, [&](const auto &tab) {

@@ -3872,12 +3872,12 @@ okm_status okm_combine_counts(okm_ctx *a, okm_ctx *b, okm_combine_op op, uint64_
     return OKM_OK;
 }
 
-// The two per-record readers of read batches, okm_read_depths[_device] and
-// okm_read_solid_runs[_device]: both search the table as okm_lookup_counts
+// The three per-record readers of read batches, okm_read_depths[_device],
+// okm_read_solid_runs[_device] and okm_read_count_quantiles[_device]: all search the table as okm_lookup_counts
 // searches it (TableForm::Search), batch by batch.  A batch is the caller's
 // device batch, or one chunk of host records: whole records, kDepthChunk bytes
 // (at least one record), packed and sent up through scratch sized for the
-// largest chunk.  ReadCall is what the four entry points share; how slices
+// largest chunk.  ReadCall is what the six entry points share; how slices
 // and chunks nest is each reader's own (see there).
 constexpr uint64_t kDepthChunk = uint64_t(32) << 20;
 
@@ -3909,6 +3909,7 @@ struct ReadCall {
     uint64_t max_bytes = 0, max_recs = 0;
     uint64_t *dseq = nullptr;
     ROW *drows = nullptr;
+    uint64_t row_len = 1;  // ROWs per record (the quantiles' rows are 1 + nq words)
     std::vector<uint8_t> packed;
     explicit ReadCall(okm_ctx *ctx)
         : c(ctx), scratch(*ctx->pool), tab(ctx, TableForm::Search), nslices(std::max<uint64_t>(tab.nslices, 1)) {}
@@ -3948,7 +3949,7 @@ struct ReadCall {
     // the largest chunk's bytes and rows, on the device and packed on the host
     okm_status stage() {
         OKM_TRY(scratch.get(max_bytes / 8 + 1, &dseq));
-        OKM_TRY(scratch.get(max_recs, &drows));
+        OKM_TRY(scratch.get(max_recs * row_len, &drows));
         packed.resize(max_bytes);
         return OKM_OK;
     }
@@ -3965,7 +3966,7 @@ struct ReadCall {
         return OKM_OK;
     }
     okm_status download(ROW *dst, uint64_t nr) {
-        HIP_TRY(hipMemcpyAsync(dst, drows, nr * sizeof(ROW), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(dst, drows, nr * row_len * sizeof(ROW), hipMemcpyDeviceToHost, c->stream));
         return sync(c);
     }
 };
@@ -4029,6 +4030,49 @@ okm_status solid_batch(SolidCall &d, const uint8_t *d_seq, uint64_t nb, uint64_t
     c->timer.begin(c->stream);
     launch_solid_runs(c->stream, nb, nrec, c->k, d.planes, d.tiles, rows);
     c->timer.end(c->stream, "solid_runs", 16.0 * (double)solid_plane_words(nb) + 48.0 * (double)nrec);
+    HIP_TRY(hipGetLastError());
+    return OKM_OK;
+}
+
+// Count quantiles.  Per batch:
+//   for every slice:  [launch_lookup_index, the first time]  k_quantile_counts
+//   then once:        k_quantile_init  k_depth_sep_count  scan  k_quantile_bounds  k_quantile_wave  k_quantile_block
+// The slices of a host-resident table meet in the count plane (each stores its
+// hits), not in the rows, so the chunk loop is the OUTER one, for the reason
+// and at the price the solid runs give.
+typedef ReadCall<uint64_t> QuantCall;
+// q[nq] checked, as the entry points' first step
+okm_status quant_args(const std::string &fn, const okm_quantile *q, uint32_t nq) {
+    if (!q) return fail(OKM_E_ARG, fn + ": null argument");
+    if (nq == 0 || nq > OKM_MAX_QUANTILES)
+        return fail(OKM_E_ARG, fn + ": " + std::to_string(nq) + " quantiles (1 to " +
+                                   std::to_string(OKM_MAX_QUANTILES) + " a call)");
+    for (uint32_t i = 0; i < nq; ++i)
+        if (q[i].den == 0 || q[i].num > q[i].den)
+            return fail(OKM_E_ARG, fn + ": quantile " + std::to_string(q[i].num) + "/" + std::to_string(q[i].den) +
+                                       " is not a fraction in [0, 1]");
+    return OKM_OK;
+}
+okm_status quant_prepare(QuantCall &d, uint64_t max_bytes, uint64_t max_recs, uint32_t nq) {
+    d.row_len = 1 + nq;
+    return d.prepare(quant_plane_words(max_bytes), quant_tile_words(max_bytes, max_recs));
+}
+// one device batch against every slice, into rows (device; every row is written)
+okm_status quant_batch(QuantCall &d, const uint8_t *d_seq, uint64_t nb, uint64_t nrec, const okm_quantile *q,
+                       uint32_t nq, uint64_t *rows) {
+    okm_ctx *c = d.c;
+    for (uint64_t si = 0; si < d.nslices; ++si) {
+        OKM_TRY(d.tab.upload(c->stream, si));
+        c->timer.begin(c->stream);
+        d.tab.index(c->stream, si);
+        launch_quantile_counts(c->stream, d_seq, nb, c->k, c->wide, d.tab.view(si), si == 0, d.planes);
+        // the read bytes in and the plane out, once per batch however many slices search it
+        c->timer.end(c->stream, "quantile_counts", si == 0 ? 5.0 * (double)nb : 0.0);
+    }
+    c->timer.begin(c->stream);
+    launch_quantile_select(c->stream, d_seq, nb, nrec, c->k, q, nq, d.planes, d.tiles, rows);
+    // the batch's separators, the plane at least once, the rows out
+    c->timer.end(c->stream, "quantile_select", 6.0 * (double)nb + 8.0 * (double)(1 + nq) * (double)nrec);
     HIP_TRY(hipGetLastError());
     return OKM_OK;
 }
@@ -4112,6 +4156,44 @@ okm_status okm_read_solid_runs(okm_ctx *c, const uint8_t *seq, const uint64_t *o
     OKM_TRY(d.each_chunk(seq, offsets, normalized, [&](uint64_t r0, uint64_t nr, uint64_t nb) {
         OKM_TRY(solid_batch(d, d.batch(), nb, nr, min_count, d.drows));
         return d.download(out + r0, nr);
+    }));
+    d.scratch.free_all();
+    return OKM_OK;
+}
+
+okm_status okm_read_count_quantiles_device(okm_ctx *c, const uint8_t *d_seq, uint64_t n_bytes, uint64_t n_records,
+                                           const okm_quantile *q, uint32_t nq, uint64_t *d_out) {
+    OKM_TRY(quant_args("okm_read_count_quantiles_device", q, nq));
+    OKM_TRY(read_enter(c, "okm_read_count_quantiles_device", n_records && (!d_out || (!d_seq && n_bytes)),
+                       n_bytes >> 32 || n_records >> 40, "batch too large", n_records, nullptr, nullptr));
+    if (n_records == 0) return OKM_OK;
+    if (n_bytes == 0) {  // records, all of them empty
+        HIP_TRY(hipMemsetAsync(d_out, 0, n_records * (1 + nq) * sizeof(uint64_t), c->stream));
+        return sync(c);
+    }
+    QuantCall d(c);
+    OKM_TRY(quant_prepare(d, n_bytes, n_records, nq));
+    const uint8_t *src;
+    OKM_TRY(d.aligned(d_seq, n_bytes, &src));
+    OKM_TRY(quant_batch(d, src, n_bytes, n_records, q, nq, d_out));
+    OKM_TRY(sync(c));
+    d.scratch.free_all();
+    return OKM_OK;
+}
+
+okm_status okm_read_count_quantiles(okm_ctx *c, const uint8_t *seq, const uint64_t *offsets, uint64_t n_records,
+                                    int normalized, const okm_quantile *q, uint32_t nq, uint64_t *out) {
+    OKM_TRY(quant_args("okm_read_count_quantiles", q, nq));
+    OKM_TRY(read_enter(c, "okm_read_count_quantiles", n_records && (!offsets || !out), n_records >> 40,
+                       "more than 2^40 records", n_records, seq, offsets));
+    if (n_records == 0) return OKM_OK;
+    QuantCall d(c);
+    OKM_TRY(d.cut(offsets, n_records, 32, "okm_read_count_quantiles: batch too large (one record of 2^32 bytes)"));
+    OKM_TRY(quant_prepare(d, d.max_bytes, d.max_recs, nq));
+    OKM_TRY(d.stage());
+    OKM_TRY(d.each_chunk(seq, offsets, normalized, [&](uint64_t r0, uint64_t nr, uint64_t nb) {
+        OKM_TRY(quant_batch(d, d.batch(), nb, nr, q, nq, d.drows));
+        return d.download(out + r0 * (1 + nq), nr);
     }));
     d.scratch.free_all();
     return OKM_OK;

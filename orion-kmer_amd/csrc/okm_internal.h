@@ -435,6 +435,8 @@ void launch_combine_write(void *stream, const TableView &d, const TableView &s, 
 // the last launch.  tiles: 2 * depth_tiles(n) + scan_tmp_elems(depth_tiles(n))
 // words of scratch; depth_tiles(n) < 2^31.
 uint64_t depth_tiles(uint64_t n_bytes);
+// tile_cnt[t] = the separators among the bytes of scan tile t, depth_tiles(n) words (the quantiles' bounds too).
+void launch_depth_sep_count(void *stream, const uint8_t *seq, uint64_t n, unsigned long long *tile_cnt);
 void launch_read_depths(void *stream, const uint8_t *seq, uint64_t n, uint64_t nrec, uint32_t k, bool wide,
                         const TableView &t, uint64_t min_count, bool count_windows, unsigned long long *tiles,
                         okm_read_depth *rows);
@@ -467,6 +469,25 @@ void launch_solid_mask(void *stream, const uint8_t *seq, uint64_t n, uint32_t k,
                        uint64_t min_count, bool first, unsigned long long *planes);
 void launch_solid_runs(void *stream, uint64_t n, uint64_t nrec, uint32_t k, const unsigned long long *planes,
                        unsigned long long *tiles, okm_solid_run *rows);
+
+// Per-record count quantiles (okm_quantile.hip), in two stages over a device
+// batch (records joined by separators, 16-byte aligned, 0 < n < 2^32 bytes).
+// plane: quant_plane_words(n) words, one uint32_t per position of the batch's
+// whole scan tiles.  launch_quantile_counts is launch_read_depths' scan and
+// search into that plane: the batch's first launch (`first`) writes its every
+// word (2^32 - 1: no valid window; else the clipped count, 0 when absent),
+// every later one (a further slice of a host-resident table) stores its hits.
+// launch_quantile_select then ranks every record's words where they lie into
+// rows[nrec * (1 + nq)] (windows, then the nq quantiles; r = separators before
+// the record, rows past nrec dropped, every row written).  q: host.  tiles:
+// quant_tile_words(n, nrec) words of scratch.
+uint64_t quant_plane_words(uint64_t n_bytes);
+uint64_t quant_tile_words(uint64_t n_bytes, uint64_t nrec);
+void launch_quantile_counts(void *stream, const uint8_t *seq, uint64_t n, uint32_t k, bool wide, const TableView &t,
+                            bool first, unsigned long long *plane);
+void launch_quantile_select(void *stream, const uint8_t *seq, uint64_t n, uint64_t nrec, uint32_t k,
+                            const okm_quantile *q, uint32_t nq, const unsigned long long *plane,
+                            unsigned long long *tiles, uint64_t *rows);
 
 // |A ∩ B| of sorted unique arrays (merge-path style binary search per element).
 void launch_intersect_count(void *stream, const uint64_t *a, uint64_t na, const uint64_t *b,

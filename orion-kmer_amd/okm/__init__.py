@@ -494,6 +494,31 @@ class KmerCounter:
         check(lib().okm_read_solid_runs_device(self.ctx, c_void_p(d_seq), nbytes, n_records, min_count,
                                                c_void_p(d_out)), "okm_read_solid_runs_device")
 
+    def count_quantiles(self, seqs: Sequence[bytes], quantiles: Sequence[Tuple[int, int]] = ((1, 2),),
+                        normalized: bool = False) -> np.ndarray:
+        """One row per record, (n, 1 + len(quantiles)) uint64: the record's
+        valid windows, then for every (num, den) the element at index
+        min(windows * num // den, windows - 1) of its windows' counts sorted
+        ascending, an absent k-mer counting 0 and every count clipped to
+        2^32 - 2 (okm_read_count_quantiles).  (1, 2) is the median count
+        khmer's normalize-by-median decides by; 0 for a record without
+        windows.  At most 4 quantiles a call."""
+        data, offs = pack_records(list(seqs))
+        q = np.ascontiguousarray(quantiles, dtype=np.uint32).reshape(-1, 2)  # okm_quantile {num, den}
+        out = np.zeros((len(offs) - 1, 1 + len(q)), dtype=np.uint64)
+        check(lib().okm_read_count_quantiles(self.ctx, data.ctypes.data, offs.ctypes.data, len(out),
+                                             1 if normalized else 0, q.ctypes.data, len(q), out.ctypes.data),
+              "okm_read_count_quantiles")
+        return out
+
+    def count_quantiles_device(self, d_seq: int, nbytes: int, n_records: int, d_out: int,
+                               quantiles: Sequence[Tuple[int, int]] = ((1, 2),)) -> None:
+        """count_quantiles() over a device batch (add_device_batch's layout)
+        into n_records rows of 1 + len(quantiles) uint64 in device memory."""
+        q = np.ascontiguousarray(quantiles, dtype=np.uint32).reshape(-1, 2)
+        check(lib().okm_read_count_quantiles_device(self.ctx, c_void_p(d_seq), nbytes, n_records, q.ctypes.data, len(q),
+                                                    c_void_p(d_out)), "okm_read_count_quantiles_device")
+
     def result_device(self) -> Tuple[int, int, int]:
         k = c_void_p()
         c = c_void_p()

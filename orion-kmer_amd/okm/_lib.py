@@ -197,6 +197,8 @@ PROTOTYPES = {
     "okm_group_read_depths": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_uint64, c_void_p]),
     "okm_read_solid_runs": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_uint64, c_void_p]),
     "okm_read_solid_runs_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_uint64, c_void_p]),
+    "okm_read_count_quantiles": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_void_p, c_uint32, c_void_p]),
+    "okm_read_count_quantiles_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint32, c_void_p]),
     "okm_synth_reads_device": (c_int, [c_uint64, c_uint64, c_uint64, c_uint64, c_uint64, c_uint32, c_double,
                                        c_double, c_void_p, c_int]),
     "okm_test_set": (None, [c_int, c_int64]),

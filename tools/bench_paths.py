@@ -54,6 +54,13 @@ input, warmup then timed steps bracketed by device syncs).
                      batch: the ratio of the two and stage 2's share, `solid`
                      asserted equal; the line is appended to
                      profiles/solid_runs.jsonl.
+  --workload count_quantiles okm_read_count_quantiles_device (1/2 alone, then
+                     four quantiles) of the configs[1] batch against its own
+                     counted table, pending and then dense, and of the ONT-like
+                     batch (--gbases) against its pending table; in the same
+                     process okm_read_depths_device over the same batch: the
+                     ratio of the two and the selection stage's share; the line
+                     is appended to profiles/count_quantiles.jsonl.
 
 The CPU baseline is the C restatement (oracle/) on a bounded sample, 1 thread.
 """
@@ -761,6 +768,94 @@ def wl_solid_runs(args):
     return out
 
 
+def wl_count_quantiles(args):
+    """Per-read count quantiles (the median alone, then four quantiles) beside
+    okm_read_depths_device over the same batch in the same process: the C2
+    batch against its own table, pending and then dense, and the ONT-like batch
+    of the depth workload (--gbases) against its own pending table.  Every
+    figure is a HIP-event time from the engine's timer rows (quantile_counts:
+    stage 1, the search; quantile_select: stage 2, the plane to the rows).
+    Against a read's own table every window is present: the 0/1 quantile must
+    equal the depth's min and 1/1 its max (clipped), windows its windows."""
+    k, repeats = 31, 3
+    steps = max(args.steps, 5)
+    four = ((0, 1), (1, 4), (1, 2), (1, 1))
+
+    def event_ms(c, names, fn):
+        for _ in range(args.warmup):
+            fn()
+        before = c.kernel_stats()
+        for _ in range(steps):
+            fn()
+        after = c.kernel_stats()
+        return [(after[n]["total_ms"] - before.get(n, {"total_ms": 0.0})["total_ms"]) / steps for n in names]
+
+    def run(batch, nreads, states):
+        dbuf = okm.DeviceBuffer(len(batch))
+        dbuf.upload(batch)
+        q_buf, depth_buf = okm.DeviceBuffer(40 * nreads), okm.DeviceBuffer(48 * nreads)
+
+        def check():
+            a, b = np.empty((nreads, 5), np.uint64), np.empty(nreads, okm.READ_DEPTH_DTYPE)
+            q_buf.download(a)
+            depth_buf.download(b)
+            assert np.array_equal(a[:, 0], b["windows"]) and np.array_equal(b["present"], b["windows"])
+            top = np.uint64(0xFFFFFFFE)
+            assert np.array_equal(a[:, 1], np.minimum(b["min"], top)) and np.array_equal(a[:, 4], np.minimum(b["max"], top))
+            assert (a[:, 1] <= a[:, 2]).all() and (a[:, 2] <= a[:, 3]).all() and (a[:, 3] <= a[:, 4]).all()
+            return int(a[:, 0].sum())
+
+        reps = []
+        with okm.KmerCounter(k) as c:
+            for rep in range(repeats):
+                c.reset()
+                c.add_device_batch(dbuf.address, len(batch))
+                distinct = c.count()
+                c.set_timing(True)
+                r = {}
+                for which in states:
+                    if which == "dense":
+                        c.result_device()
+                    for name, qs in (("median", ((1, 2),)), ("four", four)):
+                        r[f"counts_{name}_{which}_ms"], r[f"select_{name}_{which}_ms"] = event_ms(
+                            c, ("quantile_counts", "quantile_select"),
+                            lambda: c.count_quantiles_device(dbuf.address, len(batch), nreads, q_buf.address, qs))
+                    r[f"depth_{which}_ms"], = event_ms(
+                        c, ("read_depths",), lambda: c.read_depths_device(dbuf.address, len(batch), nreads, depth_buf.address, 2))
+                    windows = check()
+                reps.append(r)
+                log(json.dumps(r))
+        for b in (dbuf, q_buf, depth_buf):
+            b.free()
+
+        def med(name):
+            return sorted(r[name] for r in reps)[len(reps) // 2]
+
+        def side(which, name):
+            s1, s2, d = med(f"counts_{name}_{which}_ms"), med(f"select_{name}_{which}_ms"), med(f"depth_{which}_ms")
+            return {"quantile_counts_ms": round(s1, 4), "quantile_select_ms": round(s2, 4), "total_ms": round(s1 + s2, 4),
+                    "read_depths_ms": round(d, 4), "ratio_to_read_depths": round((s1 + s2) / d, 4),
+                    "select_share": round(s2 / (s1 + s2), 4), "select_over_counts": round(s2 / s1, 4)}
+
+        return {"reads": nreads, "bases": len(batch) - nreads, "windows": windows, "distinct": int(distinct),
+                **{f"{which}_{name}": side(which, name) for which in states for name in ("median", "four")},
+                "repeats": reps}
+
+    c2 = run(c2_batch(), READS, ("pending", "dense"))
+    ont = run(*ont_batch(args.gbases), ("pending",))
+    out = {"metric": "per-read median k-mer count of the C2 batch against its own pending table (k=31) on one MI355X, "
+                     "HIP-event ms", "value": c2["pending_median"]["total_ms"], "unit": "ms", "n_gpus": 1, "steps": steps,
+           "warmup": args.warmup, "higher_is_better": False, "dtype": "u64 keys, u32 staged counts, u32 count plane",
+           "data": "synthetic (BASELINE configs[1] reads; ONT-like long reads; device-resident)",
+           "config": {"workload": "count_quantiles: a batch counted, then its reads' count quantiles (1/2 alone; 0/1, 1/4, "
+                                  "1/2, 1/1) and their depths taken from the same device batch", "k": k,
+                      "ont_gbases": args.gbases, "repeats": repeats},
+           "c2": c2, "ont": ont}
+    with open(os.path.join(ROOT, "profiles", "count_quantiles.jsonl"), "a") as f:
+        f.write(json.dumps(out) + "\n")
+    return out
+
+
 def ont_batch(gbases: float, seed: int = 4):
     """ONT-like reads (okm.workloads.c4_reads): lognormal
     lengths (median 2,891, sigma 1.085, 200..100k), either strand, 5 %
@@ -1274,7 +1369,7 @@ def wl_classify(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth", "compare", "combine", "solid_runs"],
+    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth", "compare", "combine", "solid_runs", "count_quantiles"],
                     required=True)
     ap.add_argument("--no-ref", action="store_true", help="c3: skip the one-GPU reference table")
     ap.add_argument("--c3-reads", type=int, default=C3_READS,
@@ -1299,7 +1394,7 @@ def main():
     c5 = wl_c5_dist if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.loopback else wl_c5
     out = {"query": wl_query, "build": wl_build, "wide": wl_wide, "classify": wl_classify,
            "c5": c5, "c3": wl_c3_loop, "histogram": wl_histogram, "lookup": wl_lookup, "depth": wl_depth,
-           "compare": wl_compare, "combine": wl_combine, "solid_runs": wl_solid_runs}[args.workload](args)
+           "compare": wl_compare, "combine": wl_combine, "solid_runs": wl_solid_runs, "count_quantiles": wl_count_quantiles}[args.workload](args)
     if out is not None:
         print(json.dumps(out), flush=True)
 
