@@ -330,6 +330,67 @@ okm_status okm_read_count_quantiles_device(okm_ctx *ctx, const uint8_t *d_seq, u
                                            const okm_quantile *q /* host */, uint32_t nq,
                                            uint64_t *d_out /* device, n_records * (1 + nq) */);
 
+/* Per-record count intervals: EVERY stretch of a record whose k-mers' counts
+ * lie in a range, as BED-like rows -- what `meryl-lookup -bed` and -bed-runs
+ * print, what Merqury reads assembly errors from (assembly k-mers the read
+ * table lacks), what KAT sect and repeat masking by high-count k-mers need; an
+ * extension, the reference has none.  Slot j of a record is the window that
+ * starts at its base j (after normalisation).  A slot is SELECTED when its
+ * window holds A/C/G/T only (either case, U as T) and lo <= c <= hi, where c
+ * is the count of its canonical k-mer and an absent k-mer counts 0.  So lo = 0
+ * selects the k-mers the table LACKS -- unlike min_count elsewhere, where 0
+ * behaves as 1 -- and an invalid window is never selected:
+ *   lo = 0, hi = 0            what the table lacks
+ *   lo = m, hi = 2^64 - 1     the solid slots of okm_read_solid_runs
+ *   lo = 0, hi = 2^64 - 1     every valid window, whatever the table holds
+ * Rows ascend by (record, start); a record without intervals has no row; an
+ * interval never crosses records (a selected window holds no separator).  The
+ * rows are found on the device from okm_read_solid_runs' two bit planes, by
+ * ranking the run starts with a scan; the read bytes are searched once and the
+ * table stays where and as it lies.
+ * There is no group form, for okm_read_solid_runs' reason: intervals taken
+ * against owners of disjoint key ranges do not combine by any rule on the rows
+ * (a stretch may alternate between owners, and with lo = 0 every owner selects
+ * what the others hold), only in the owners' bit planes, which never leave the
+ * device. */
+typedef enum okm_interval_unit {
+    OKM_INTERVAL_BASES = 0,  /* bases covered by a selected window, overlapping and abutting stretches merged:
+                                a run [s, e) of selected slots covers bases [s, e + k - 1); two runs whose gap
+                                in slots is at most k - 1 give one row, a gap of k (a single N) two rows one
+                                base apart */
+    OKM_INTERVAL_SLOTS = 1   /* maximal runs of selected window starts, in slot coordinates */
+} okm_interval_unit;
+typedef struct okm_count_interval {
+    uint64_t record;  /* index of the record */
+    uint64_t start;   /* 0-based, in the record after normalisation */
+    uint64_t end;     /* half-open */
+} okm_count_interval;
+/* *out = the rows, *n of them, in library memory (okm_free_result); NULL when
+ * there are none.  Everything else as okm_read_solid_runs: the record layout
+ * and `normalized`, counts first if batches are pending, read-only on the
+ * table in every representation, host records go up in chunks of whole
+ * records (`record` is the index in the call), k > 32 contexts alike.  The
+ * device memory for a chunk's rows is taken at the chunk's counted total.
+ * n_records == 0: OK, *n = 0, *out = NULL, nothing touched.  A set-mode
+ * context has no counts: OKM_E_STATE.  A null argument, lo > hi, an unknown
+ * unit, one chunk -- so in effect one record -- of 2^32 bytes or more:
+ * OKM_E_ARG.  On any failure nothing is returned. */
+okm_status okm_read_count_intervals(okm_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, uint64_t n_records,
+                                    int normalized, uint64_t lo, uint64_t hi, okm_interval_unit unit,
+                                    okm_count_interval **out /* library memory, okm_free_result */, uint64_t *n);
+/* The same over a device batch, as okm_read_solid_runs_device takes it (a
+ * record's index is the number of separators before it, records past
+ * n_records give no rows, an unterminated last record is taken as it stands,
+ * bytes at and beyond n_bytes are never looked at).  *n is always the full
+ * number of intervals; the first min(*n, cap) rows are written and no row
+ * behind them is touched.  *n > cap with a non-null d_out: OKM_E_OVERFLOW, the
+ * written rows are valid.  d_out == NULL with cap == 0 is the count-only call:
+ * OKM_OK.  n_bytes >= 2^32: OKM_E_ARG (batch too large). */
+okm_status okm_read_count_intervals_device(okm_ctx *ctx, const uint8_t *d_seq, uint64_t n_bytes, uint64_t n_records,
+                                           uint64_t lo, uint64_t hi, okm_interval_unit unit,
+                                           okm_count_interval *d_out /* device, cap rows; may be NULL when cap == 0 */,
+                                           uint64_t cap, uint64_t *n /* host */);
+
 /* Two counted tables compared: the keys both hold, with their counts -- what
  * `kmc_tools simple intersect` with counters_min, or two jellyfish tables,
  * answer; an extension, the reference's compare works on keys alone.  An entry

@@ -220,7 +220,7 @@ static const char *kVersion = "orion-kmer 0.1.0";
 
 static void print_help(const std::string &cmd) {
     if (cmd == "count")
-        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n      --depth <FASTX>              Take the k-mer depth of every record of FASTX in the whole table (extension)\n      --depth-output <FILE>        Where --depth writes id<TAB>windows<TAB>present<TAB>solid<TAB>sum<TAB>min<TAB>max, in input order\n      --depth-min-count <N>        A window is solid when its k-mer's count is at least N [default: 2]\n      --solid-runs <FASTX>         Find the solid runs of every record of FASTX in the whole table: where its solid k-mers lie (extension)\n      --solid-runs-output <FILE>   Where --solid-runs writes id<TAB>slots<TAB>solid<TAB>run_start<TAB>run_len<TAB>lead<TAB>trail, in input order\n      --solid-runs-min-count <N>   A slot is solid when its k-mer's count is at least N [default: 2]\n      --quantiles <FASTX>          Per record of FASTX: quantiles of its k-mers' counts in the table, the median by default (extension)\n      --quantiles-output <FILE>    Where --quantiles writes id<TAB>windows<TAB>one value per quantile, in input order\n      --quantiles-at <A/B,...>     Up to 4 fractions: the sorted counts' element at index windows * A / B [default: 1/2]\n      --compare <FASTX>           Count FASTX as a second table (same k) and compare the two tables with their counts (extension)\n      --compare-output <FILE>      Where --compare writes field<TAB>value: the shared k-mers, their counts, Jaccard, weighted Jaccard, Bray-Curtis\n      --compare-min-count <N>      Minimum count of a k-mer of the --compare table (--min-count: of the first table) [default: 1]\n      --combine <FASTX>            Count FASTX as a second table (same k) and combine the two tables into a third (extension)\n      --combine-op <OP>            union, intersect, intersect_left, difference or subtract (the first table is the left one)\n      --combine-output <FILE>      Where --combine writes the combined table as KMER<TAB>COUNT lines\n      --combine-min-count <N>      Minimum count of a k-mer of the --combine table (--min-count: of the first table) [default: 1]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
+        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n      --depth <FASTX>              Take the k-mer depth of every record of FASTX in the whole table (extension)\n      --depth-output <FILE>        Where --depth writes id<TAB>windows<TAB>present<TAB>solid<TAB>sum<TAB>min<TAB>max, in input order\n      --depth-min-count <N>        A window is solid when its k-mer's count is at least N [default: 2]\n      --solid-runs <FASTX>         Find the solid runs of every record of FASTX in the whole table: where its solid k-mers lie (extension)\n      --solid-runs-output <FILE>   Where --solid-runs writes id<TAB>slots<TAB>solid<TAB>run_start<TAB>run_len<TAB>lead<TAB>trail, in input order\n      --solid-runs-min-count <N>   A slot is solid when its k-mer's count is at least N [default: 2]\n      --quantiles <FASTX>          Per record of FASTX: quantiles of its k-mers' counts in the table, the median by default (extension)\n      --quantiles-output <FILE>    Where --quantiles writes id<TAB>windows<TAB>one value per quantile, in input order\n      --quantiles-at <A/B,...>     Up to 4 fractions: the sorted counts' element at index windows * A / B [default: 1/2]\n      --intervals <FASTX>          Per record of FASTX: the stretches whose k-mers' counts in the table lie in a range, as BED (extension)\n      --intervals-output <FILE>    Where --intervals writes id<TAB>start<TAB>end, 0-based and half-open, in input order\n      --intervals-min-count <N>    The range's lower end; 0 selects the k-mers the table lacks [default: 2]\n      --intervals-max-count <N>    The range's upper end [default: unbounded]\n      --intervals-slots            Intervals of window starts, not of the bases the windows cover\n      --compare <FASTX>          Count FASTX as a second table (same k) and compare the two tables with their counts (extension)\n      --compare-output <FILE>      Where --compare writes field<TAB>value: the shared k-mers, their counts, Jaccard, weighted Jaccard, Bray-Curtis\n      --compare-min-count <N>      Minimum count of a k-mer of the --compare table (--min-count: of the first table) [default: 1]\n      --combine <FASTX>            Count FASTX as a second table (same k) and combine the two tables into a third (extension)\n      --combine-op <OP>            union, intersect, intersect_left, difference or subtract (the first table is the left one)\n      --combine-output <FILE>      Where --combine writes the combined table as KMER<TAB>COUNT lines\n      --combine-min-count <N>      Minimum count of a k-mer of the --combine table (--min-count: of the first table) [default: 1]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
     else if (cmd == "build")
         printf("Build a unique k-mer database from genome assemblies\n\nUsage: orion-kmer build [OPTIONS] --kmer-size <KMER_SIZE> --genomes <GENOME_FILES>... --output-file <OUTPUT_FILE>\n");
     else if (cmd == "compare")
@@ -459,6 +459,35 @@ static int write_read_rows(okm_reader *r, const std::string &path, const std::st
     return 0;
 }
 
+// --intervals: every batch of the reader through okm_read_count_intervals, one
+// BED line per interval, id<TAB>start<TAB>end, in input order.  A record has
+// any number of lines, none included, so write_read_rows' fixed rows do not fit.
+static int write_intervals(okm_ctx *ctx, okm_reader *r, const std::string &path, const std::string &out_path,
+                           uint64_t lo, uint64_t hi, okm_interval_unit unit) {
+    std::string lines;
+    for (;;) {
+        const uint8_t *seq, *ids;
+        const uint64_t *off, *ioff;
+        uint64_t n, ni = 0;
+        if (okm_reader_next(r, 128ull << 20, &seq, &off, &n) != OKM_OK)
+            return die("Error reading record from " + path);
+        if (n == 0) break;
+        okm_reader_ids(r, &ids, &ioff);
+        okm_count_interval *iv = nullptr;
+        if (!ctx || okm_read_count_intervals(ctx, seq, off, n, 1, lo, hi, unit, &iv, &ni) != OKM_OK)
+            return die("GPU engine failure while finding count intervals: " + err_detail());
+        for (uint64_t i = 0; i < ni; ++i) {
+            lines.append(reinterpret_cast<const char *>(ids + ioff[iv[i].record]),
+                         ioff[iv[i].record + 1] - ioff[iv[i].record]);
+            lines += '\t' + std::to_string(iv[i].start) + '\t' + std::to_string(iv[i].end) + '\n';
+        }
+        okm_free_result(iv);
+    }
+    if (okm_write_file(out_path.c_str(), reinterpret_cast<const uint8_t *>(lines.data()), lines.size()) != OKM_OK)
+        return die("Failed to get output writer for intervals output file: " + dbg_path(out_path));
+    return 0;
+}
+
 // --compare: the second input counted into a context of its own beside the
 // first table's (one GPU), okm_compare_counts of the two, and field<TAB>value
 // lines: the eight fields, then the ratios that follow from them, printed with
@@ -593,6 +622,27 @@ static int run_count(const Args &a) {
         return usage_error("invalid value '" + qta + "' for '--quantiles-at <A/B,...>'");
     if (want_qt && g_gpus != 1)
         return usage_error("the argument '--quantiles <FASTX>' cannot be used with '--gpus <GPUS>' other than 1");
+    // --intervals <FASTX> --intervals-output <FILE> [--intervals-min-count <N>]
+    // [--intervals-max-count <N>] [--intervals-slots]: per record of FASTX, the
+    // stretches whose k-mers' counts in the WHOLE table lie in [min, max], as
+    // BED lines (meryl-lookup -bed; an extension).  A min of 0 selects the
+    // k-mers the table lacks.  The two flags need one another and the others
+    // need them.  One GPU only: the owners' rows do not combine.
+    std::string iv_path, iv_out, ivlo, ivhi;
+    const bool want_iv = get_one(a, "intervals", iv_path), has_ivout = get_one(a, "intervals-output", iv_out);
+    const bool has_ivlo = get_one(a, "intervals-min-count", ivlo), has_ivhi = get_one(a, "intervals-max-count", ivhi);
+    std::string ivflag;
+    const bool iv_slots = get_one(a, "intervals-slots", ivflag);
+    if (want_iv != has_ivout || ((has_ivlo || has_ivhi || iv_slots) && !want_iv))
+        return usage_error(std::string("the following required arguments were not provided:\n  ") +
+                           (want_iv ? "--intervals-output <FILE>" : "--intervals <FASTX>"));
+    uint64_t iv_lo = 2, iv_hi = ~0ull;
+    if (has_ivlo && !parse_u64(ivlo, iv_lo))
+        return usage_error("invalid value '" + ivlo + "' for '--intervals-min-count <N>'");
+    if (has_ivhi && (!parse_u64(ivhi, iv_hi) || iv_hi < iv_lo))
+        return usage_error("invalid value '" + ivhi + "' for '--intervals-max-count <N>'");
+    if (want_iv && g_gpus != 1)
+        return usage_error("the argument '--intervals <FASTX>' cannot be used with '--gpus <GPUS>' other than 1");
     // --compare <FASTX> --compare-output <FILE> [--compare-min-count <N>]: FASTX
     // is counted at the same k into a second table and the two tables are
     // compared with their counts (kmc_tools intersect with counters_min; an
@@ -668,6 +718,12 @@ static int run_count(const Args &a) {
         const okm_status ds = okm_reader_open2(&quant_reader.r, qt_path.c_str(), 1, OKM_READ_IDS);
         if (ds == OKM_E_IO) return die("Failed to get input reader for quantiles file: " + dbg_path(qt_path));
         if (ds != OKM_OK) return die("Failed to parse FASTA/Q content from quantiles file: " + dbg_path(qt_path));
+    }
+    ReadsReader ival_reader;  // the --intervals reads, likewise
+    if (want_iv) {
+        const okm_status ds = okm_reader_open2(&ival_reader.r, iv_path.c_str(), 1, OKM_READ_IDS);
+        if (ds == OKM_E_IO) return die("Failed to get input reader for intervals file: " + dbg_path(iv_path));
+        if (ds != OKM_OK) return die("Failed to parse FASTA/Q content from intervals file: " + dbg_path(iv_path));
     }
     // one table across all inputs (count.rs:48), on g_gpus GPUs (default 1),
     // started while the first input is parsed
@@ -746,6 +802,13 @@ static int run_count(const Args &a) {
             return rc;
         info("orion_kmer::commands::count", "Successfully wrote the count quantiles to " + dbg_path(qt_out));
         phase("quantiles");
+    }
+    if (want_iv) {  // the reads go to two bit planes and those to the intervals; the table stays as it lies
+        if ((rc = write_intervals(okm_group_owner(grp, 0), ival_reader.r, iv_path, iv_out, iv_lo, iv_hi,
+                                  iv_slots ? OKM_INTERVAL_SLOTS : OKM_INTERVAL_BASES)))
+            return rc;
+        info("orion_kmer::commands::count", "Successfully wrote the count intervals to " + dbg_path(iv_out));
+        phase("intervals");
     }
     if (want_cmp) {  // both tables are merged as their counts left them
         if ((rc = write_compare(okm_group_owner(grp, 0), k, wide, cmp_path, cmp_out, min_count, cmp_min))) return rc;
@@ -1316,6 +1379,11 @@ int main(int argc, char **argv) {
         spec.push_back({"quantiles", 0, true, false});
         spec.push_back({"quantiles-output", 0, true, false});
         spec.push_back({"quantiles-at", 0, true, false});
+        spec.push_back({"intervals", 0, true, false});
+        spec.push_back({"intervals-output", 0, true, false});
+        spec.push_back({"intervals-min-count", 0, true, false});
+        spec.push_back({"intervals-max-count", 0, true, false});
+        spec.push_back({"intervals-slots", 0, false, false});
         spec.push_back({"compare", 0, true, false});
         spec.push_back({"compare-output", 0, true, false});
         spec.push_back({"compare-min-count", 0, true, false});

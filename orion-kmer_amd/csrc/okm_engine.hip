@@ -3872,12 +3872,13 @@ okm_status okm_combine_counts(okm_ctx *a, okm_ctx *b, okm_combine_op op, uint64_
     return OKM_OK;
 }
 
-// The three per-record readers of read batches, okm_read_depths[_device],
-// okm_read_solid_runs[_device] and okm_read_count_quantiles[_device]: all search the table as okm_lookup_counts
+// The four per-record readers of read batches, okm_read_depths[_device],
+// okm_read_solid_runs[_device], okm_read_count_quantiles[_device] and
+// okm_read_count_intervals[_device]: all search the table as okm_lookup_counts
 // searches it (TableForm::Search), batch by batch.  A batch is the caller's
 // device batch, or one chunk of host records: whole records, kDepthChunk bytes
 // (at least one record), packed and sent up through scratch sized for the
-// largest chunk.  ReadCall is what the six entry points share; how slices
+// largest chunk.  ReadCall is what the eight entry points share; how slices
 // and chunks nest is each reader's own (see there).
 constexpr uint64_t kDepthChunk = uint64_t(32) << 20;
 
@@ -4076,6 +4077,61 @@ okm_status quant_batch(QuantCall &d, const uint8_t *d_seq, uint64_t nb, uint64_t
     HIP_TRY(hipGetLastError());
     return OKM_OK;
 }
+
+// Count intervals.  Per batch:
+//   for every slice:  [launch_lookup_index, the first time]  k_interval_mask
+//   then once:        k_interval_tiles  scan  scan  k_interval_bounds
+//   then:             k_interval_emit, the total read back behind it
+// The slices of a host-resident table meet in the selection bit plane (a hit
+// overrides the bit), so the chunk loop is the OUTER one, for the reason and at
+// the price the solid runs give.  The rows have no fixed number: the device
+// form emits under the caller's capacity; the host form emits twice per chunk,
+// first with no capacity at all, which only counts, then into scratch taken at
+// exactly that total (the worst case, a row per two bytes, is 12 times the
+// chunk).  The second pass reads the planes again, n / 4 bytes.
+typedef ReadCall<okm_count_interval> IntervalCall;
+okm_status interval_args(const std::string &fn, uint64_t lo, uint64_t hi, okm_interval_unit unit) {
+    if (lo > hi) return fail(OKM_E_ARG, fn + ": lo " + std::to_string(lo) + " is above hi " + std::to_string(hi));
+    if ((int)unit != OKM_INTERVAL_BASES && (int)unit != OKM_INTERVAL_SLOTS)
+        return fail(OKM_E_ARG, fn + ": unknown unit " + std::to_string((int)unit));
+    return OKM_OK;
+}
+okm_status interval_prepare(IntervalCall &d, uint64_t max_bytes, uint64_t max_recs) {
+    return d.prepare(2 * solid_plane_words(max_bytes), interval_tile_words(max_bytes, max_recs));
+}
+// one device batch (nb > 0) against every slice, into the planes
+okm_status interval_search(IntervalCall &d, const uint8_t *d_seq, uint64_t nb, uint64_t lo, uint64_t hi) {
+    okm_ctx *c = d.c;
+    for (uint64_t si = 0; si < d.nslices; ++si) {
+        OKM_TRY(d.tab.upload(c->stream, si));
+        c->timer.begin(c->stream);
+        d.tab.index(c->stream, si);
+        launch_interval_mask(c->stream, d_seq, nb, c->k, c->wide, d.tab.view(si), lo, hi, si == 0, d.planes);
+        // the read bytes in, once per batch however many slices search it; the rows are stage 2's
+        c->timer.end(c->stream, "interval_mask", si == 0 ? (double)nb : 0.0);
+    }
+    HIP_TRY(hipGetLastError());
+    return OKM_OK;
+}
+// The planes into rows[0 .. min(*total, cap)) (device; null when cap == 0) and
+// *total; `index`: the batch's first emit, which ranks the runs beforehand.
+okm_status interval_emit(IntervalCall &d, uint64_t nb, uint64_t nrec, bool slots, bool index, uint64_t rec0,
+                         okm_count_interval *rows, uint64_t cap, uint64_t *total) {
+    okm_ctx *c = d.c;
+    c->timer.begin(c->stream);
+    if (index) launch_interval_index(c->stream, nb, nrec, c->k, slots, d.planes, d.tiles);
+    const unsigned long long *d_total = launch_interval_rows(c->stream, nb, nrec, c->k, slots, d.planes, d.tiles, rec0,
+                                                             rows, cap);
+    // both planes in, once per batch; the rows out are added below
+    c->timer.end(c->stream, "interval_rows", index ? 16.0 * (double)solid_plane_words(nb) : 0.0);
+    HIP_TRY(hipGetLastError());
+    unsigned long long t = 0;
+    HIP_TRY(hipMemcpyAsync(&t, d_total, sizeof(t), hipMemcpyDeviceToHost, c->stream));
+    OKM_TRY(sync(c));
+    *total = t;
+    c->timer.add_bytes("interval_rows", (double)sizeof(okm_count_interval) * (double)std::min<uint64_t>(t, cap));
+    return OKM_OK;
+}
 }  // namespace
 }  // extern "C++"
 
@@ -4196,6 +4252,72 @@ okm_status okm_read_count_quantiles(okm_ctx *c, const uint8_t *seq, const uint64
         return d.download(out + r0 * (1 + nq), nr);
     }));
     d.scratch.free_all();
+    return OKM_OK;
+}
+
+okm_status okm_read_count_intervals_device(okm_ctx *c, const uint8_t *d_seq, uint64_t n_bytes, uint64_t n_records,
+                                           uint64_t lo, uint64_t hi, okm_interval_unit unit, okm_count_interval *d_out,
+                                           uint64_t cap, uint64_t *n) {
+    const std::string fn = "okm_read_count_intervals_device";
+    if (n) *n = 0;
+    OKM_TRY(interval_args(fn, lo, hi, unit));
+    OKM_TRY(read_enter(c, fn, !n || (!d_out && cap) || (n_records && !d_seq && n_bytes),
+                       n_bytes >> 32 || n_records >> 40, "batch too large", n_records, nullptr, nullptr));
+    if (n_records == 0 || n_bytes == 0) return OKM_OK;  // no records, or all of them empty: no rows
+    IntervalCall d(c);
+    OKM_TRY(interval_prepare(d, n_bytes, n_records));
+    const uint8_t *src;
+    OKM_TRY(d.aligned(d_seq, n_bytes, &src));
+    OKM_TRY(interval_search(d, src, n_bytes, lo, hi));
+    uint64_t total = 0;
+    OKM_TRY(interval_emit(d, n_bytes, n_records, unit == OKM_INTERVAL_SLOTS, true, 0, d_out, cap, &total));
+    d.scratch.free_all();
+    *n = total;
+    if (d_out && total > cap)
+        return fail(OKM_E_OVERFLOW, fn + ": " + std::to_string(total) + " intervals, room for " + std::to_string(cap));
+    return OKM_OK;
+}
+
+okm_status okm_read_count_intervals(okm_ctx *c, const uint8_t *seq, const uint64_t *offsets, uint64_t n_records,
+                                    int normalized, uint64_t lo, uint64_t hi, okm_interval_unit unit,
+                                    okm_count_interval **out, uint64_t *n) {
+    const std::string fn = "okm_read_count_intervals";
+    if (out) *out = nullptr;
+    if (n) *n = 0;
+    OKM_TRY(interval_args(fn, lo, hi, unit));
+    OKM_TRY(read_enter(c, fn, !out || !n || (n_records && !offsets), n_records >> 40, "more than 2^40 records",
+                       n_records, seq, offsets));
+    if (n_records == 0) return OKM_OK;
+    IntervalCall d(c);
+    OKM_TRY(d.cut(offsets, n_records, 32, "okm_read_count_intervals: batch too large (one record of 2^32 bytes)"));
+    OKM_TRY(interval_prepare(d, d.max_bytes, d.max_recs));
+    // stage()'s bytes without its rows: a chunk's rows are taken when their number is known
+    OKM_TRY(d.scratch.get(d.max_bytes / 8 + 1, &d.dseq));
+    d.packed.resize(d.max_bytes);
+    const bool slots = unit == OKM_INTERVAL_SLOTS;
+    std::unique_ptr<okm_count_interval, decltype(&std::free)> res(nullptr, &std::free);
+    uint64_t have = 0;
+    OKM_TRY(d.each_chunk(seq, offsets, normalized, [&](uint64_t r0, uint64_t nr, uint64_t nb) {
+        uint64_t total = 0, again = 0;
+        OKM_TRY(interval_search(d, d.batch(), nb, lo, hi));
+        OKM_TRY(interval_emit(d, nb, nr, slots, true, r0, nullptr, 0, &total));
+        if (total == 0) return OKM_OK;
+        void *grown = std::realloc(res.get(), (have + total) * sizeof(okm_count_interval));
+        if (!grown) return fail(OKM_E_NOMEM, fn + ": host allocation");
+        res.release();
+        res.reset(static_cast<okm_count_interval *>(grown));
+        OKM_TRY(d.scratch.get(total, &d.drows));
+        OKM_TRY(interval_emit(d, nb, nr, slots, false, r0, d.drows, total, &again));
+        HIP_TRY(hipMemcpyAsync(res.get() + have, d.drows, total * sizeof(okm_count_interval), hipMemcpyDeviceToHost,
+                               c->stream));
+        OKM_TRY(sync(c));
+        d.scratch.put(d.drows);
+        have += total;
+        return OKM_OK;
+    }));
+    d.scratch.free_all();
+    *out = res.release();
+    *n = have;
     return OKM_OK;
 }
 

@@ -489,6 +489,26 @@ void launch_quantile_select(void *stream, const uint8_t *seq, uint64_t n, uint64
                             const okm_quantile *q, uint32_t nq, const unsigned long long *plane,
                             unsigned long long *tiles, uint64_t *rows);
 
+// Per-record count intervals (okm_interval.hip), over a device batch as the
+// solid runs take it and in their planes (2 * solid_plane_words(n) words).
+// launch_interval_mask is launch_solid_mask with the predicate lo <= count <=
+// hi, an absent k-mer counting 0: the first launch writes both planes whole,
+// every later one (a further slice of a host-resident table) overrides the bits
+// of the windows it holds.  launch_interval_index then ranks the runs (of
+// slots, or of the bases their windows cover) and the records into tiles,
+// interval_tile_words(n, nrec) words of scratch, and launch_interval_rows,
+// any number of times after it, writes rows[0 .. min(total, cap)) (rows may be
+// null when cap == 0; records numbered from rec0; no row of a record past nrec)
+// and returns the device word that holds the total.
+uint64_t interval_tile_words(uint64_t n_bytes, uint64_t nrec);
+void launch_interval_mask(void *stream, const uint8_t *seq, uint64_t n, uint32_t k, bool wide, const TableView &t,
+                          uint64_t lo, uint64_t hi, bool first, unsigned long long *planes);
+void launch_interval_index(void *stream, uint64_t n, uint64_t nrec, uint32_t k, bool slots,
+                           const unsigned long long *planes, unsigned long long *tiles);
+const unsigned long long *launch_interval_rows(void *stream, uint64_t n, uint64_t nrec, uint32_t k, bool slots,
+                                               const unsigned long long *planes, unsigned long long *tiles,
+                                               uint64_t rec0, okm_count_interval *rows, uint64_t cap);
+
 // |A ∩ B| of sorted unique arrays (merge-path style binary search per element).
 void launch_intersect_count(void *stream, const uint64_t *a, uint64_t na, const uint64_t *b,
                             uint64_t nb, unsigned long long *out, bool wide);

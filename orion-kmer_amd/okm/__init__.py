@@ -165,6 +165,9 @@ class DeviceBuffer:
 READ_DEPTH_DTYPE = np.dtype([(f, "<u8") for f in ("windows", "present", "solid", "sum", "min", "max")])
 # okm_solid_run (include/orion_kmer.h): six u64 per record
 SOLID_RUN_DTYPE = np.dtype([(f, "<u8") for f in ("slots", "solid", "run_start", "run_len", "lead", "trail")])
+# okm_count_interval (include/orion_kmer.h): three u64 per interval; okm_interval_unit
+COUNT_INTERVAL_DTYPE = np.dtype([(f, "<u8") for f in ("record", "start", "end")])
+INTERVAL_UNITS = {"bases": 0, "slots": 1}
 
 
 def pack_records(seqs: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
@@ -518,6 +521,41 @@ class KmerCounter:
         q = np.ascontiguousarray(quantiles, dtype=np.uint32).reshape(-1, 2)
         check(lib().okm_read_count_quantiles_device(self.ctx, c_void_p(d_seq), nbytes, n_records, q.ctypes.data, len(q),
                                                     c_void_p(d_out)), "okm_read_count_quantiles_device")
+
+    def count_intervals(self, seqs: Sequence[bytes], lo: int, hi: int, unit: str = "bases",
+                        normalized: bool = False) -> np.ndarray:
+        """One row per interval (COUNT_INTERVAL_DTYPE: record, start, end;
+        0-based, half-open, ascending by (record, start)): every maximal
+        stretch of a record whose k-mers' counts lie in [lo, hi], an absent
+        k-mer counting 0 -- so lo = 0 selects what the table lacks
+        (okm_read_count_intervals).  unit "bases": the bases the selected
+        windows cover, overlapping and abutting stretches merged; "slots":
+        runs of selected window starts."""
+        data, offs = pack_records(list(seqs))
+        ptr, n = c_void_p(), c_uint64()
+        check(lib().okm_read_count_intervals(self.ctx, data.ctypes.data, offs.ctypes.data, len(offs) - 1,
+                                             1 if normalized else 0, lo, hi, INTERVAL_UNITS[unit], byref(ptr),
+                                             byref(n)), "okm_read_count_intervals")
+        try:
+            out = np.empty(n.value, dtype=COUNT_INTERVAL_DTYPE)
+            if n.value:
+                ctypes.memmove(out.ctypes.data, ptr.value, out.nbytes)
+            return out
+        finally:
+            lib().okm_free_result(ptr)
+
+    def count_intervals_device(self, d_seq: int, nbytes: int, n_records: int, d_out: int, cap: int, lo: int, hi: int,
+                               unit: str = "bases") -> int:
+        """count_intervals() over a device batch (add_device_batch's layout)
+        into at most cap rows of 24 bytes in device memory; returns the full
+        number of intervals.  d_out = 0 with cap = 0 only counts; more
+        intervals than cap raise OkmError (OKM_E_OVERFLOW), the first cap rows
+        written."""
+        n = c_uint64()
+        check(lib().okm_read_count_intervals_device(self.ctx, c_void_p(d_seq), nbytes, n_records, lo, hi,
+                                                    INTERVAL_UNITS[unit], c_void_p(d_out), cap, byref(n)),
+              "okm_read_count_intervals_device")
+        return n.value
 
     def result_device(self) -> Tuple[int, int, int]:
         k = c_void_p()

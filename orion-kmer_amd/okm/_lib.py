@@ -199,6 +199,10 @@ PROTOTYPES = {
     "okm_read_solid_runs_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_uint64, c_void_p]),
     "okm_read_count_quantiles": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_void_p, c_uint32, c_void_p]),
     "okm_read_count_quantiles_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint32, c_void_p]),
+    "okm_read_count_intervals": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_uint64, c_uint64, c_int,
+                                         POINTER(c_void_p), _P64]),
+    "okm_read_count_intervals_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_uint64, c_uint64, c_int,
+                                                c_void_p, c_uint64, _P64]),
     "okm_synth_reads_device": (c_int, [c_uint64, c_uint64, c_uint64, c_uint64, c_uint64, c_uint32, c_double,
                                        c_double, c_void_p, c_int]),
     "okm_test_set": (None, [c_int, c_int64]),

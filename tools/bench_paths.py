@@ -61,6 +61,13 @@ input, warmup then timed steps bracketed by device syncs).
                      process okm_read_depths_device over the same batch: the
                      ratio of the two and the selection stage's share; the line
                      is appended to profiles/count_quantiles.jsonl.
+  --workload count_intervals okm_read_count_intervals_device (lo = 2 in bases
+                     and in slots, lo = hi = 0) of the configs[1] batch against
+                     its own counted table, pending and then dense, and in the
+                     same process okm_read_solid_runs_device over the same
+                     batch: stage 2's ratio to the solid runs' stage 2, the
+                     SLOTS rows' slots asserted to add up to `solid`; the line
+                     is appended to profiles/count_intervals.jsonl.
 
 The CPU baseline is the C restatement (oracle/) on a bounded sample, 1 thread.
 """
@@ -768,6 +775,92 @@ def wl_solid_runs(args):
     return out
 
 
+def wl_count_intervals(args):
+    """Per-read count intervals of the C2 batch against its own table, pending
+    and then dense (result_device() gathers): lo = 2 in both units and lo = hi
+    = 0 (what the table lacks), beside okm_read_solid_runs_device over the same
+    batch in the same process; every figure is a HIP-event time from the
+    engine's timer rows (interval_mask: stage 1, the search; interval_rows:
+    stage 2, the bit planes to the rows).  The slots of the SLOTS rows must add
+    up to the solid runs' `solid`."""
+    k, repeats = 31, 3
+    steps = max(args.steps, 5)
+    batch, nreads = c2_batch(), READS
+    dbuf = okm.DeviceBuffer(len(batch))
+    dbuf.upload(batch)
+    runs_buf = okm.DeviceBuffer(48 * nreads)
+    cases = {"bases": (2, (1 << 64) - 1, "bases"), "slots": (2, (1 << 64) - 1, "slots"), "absent": (0, 0, "bases")}
+
+    def event_ms(c, names, fn):
+        for _ in range(args.warmup):
+            fn()
+        before = c.kernel_stats()
+        for _ in range(steps):
+            fn()
+        after = c.kernel_stats()
+        return [(after[n]["total_ms"] - before.get(n, {"total_ms": 0.0})["total_ms"]) / steps for n in names]
+
+    reps, rows = [], {}
+    with okm.KmerCounter(k) as c:
+        for rep in range(repeats):
+            c.reset()
+            c.add_device_batch(dbuf.address, len(batch))
+            distinct = c.count()
+            c.set_timing(True)
+            r = {}
+            for which in ("pending", "dense"):
+                if which == "dense":
+                    c.result_device()
+                r[f"solid_mask_{which}_ms"], r[f"solid_runs_{which}_ms"] = event_ms(
+                    c, ("solid_mask", "solid_runs"),
+                    lambda: c.solid_runs_device(dbuf.address, len(batch), nreads, runs_buf.address, 2))
+                solid = np.empty(nreads, okm.SOLID_RUN_DTYPE)
+                runs_buf.download(solid)
+                for name, (lo, hi, unit) in cases.items():
+                    n = c.count_intervals_device(dbuf.address, len(batch), nreads, 0, 0, lo, hi, unit)  # count only
+                    out = okm.DeviceBuffer(24 * max(n, 1))
+                    r[f"{name}_mask_{which}_ms"], r[f"{name}_rows_{which}_ms"] = event_ms(
+                        c, ("interval_mask", "interval_rows"),
+                        lambda: c.count_intervals_device(dbuf.address, len(batch), nreads, out.address, n, lo, hi, unit))
+                    got = np.empty(n, okm.COUNT_INTERVAL_DTYPE)
+                    if n:
+                        out.download(got)
+                    out.free()
+                    assert (got["end"] > got["start"]).all() and (np.diff(got["record"].astype(np.int64)) >= 0).all()
+                    if name == "slots":
+                        assert int((got["end"] - got["start"]).sum()) == int(solid["solid"].sum()), \
+                            "the SLOTS rows' slots do not add up to the solid runs' solid"
+                    rows[name] = int(n)
+            reps.append(r)
+            log(json.dumps(r))
+    for b in (dbuf, runs_buf):
+        b.free()
+
+    def med(name):
+        return round(sorted(r[name] for r in reps)[len(reps) // 2], 4)
+
+    def side(which):
+        o = {"solid_mask_ms": med(f"solid_mask_{which}_ms"), "solid_runs_ms": med(f"solid_runs_{which}_ms")}
+        for name in cases:
+            o[f"{name}_mask_ms"], o[f"{name}_rows_ms"] = med(f"{name}_mask_{which}_ms"), med(f"{name}_rows_{which}_ms")
+            o[f"{name}_rows_to_solid_runs"] = round(o[f"{name}_rows_ms"] / o["solid_runs_ms"], 4)
+        return o
+
+    pend = side("pending")
+    out = {"metric": "per-read count intervals (bases, lo=2) of the C2 batch against its own pending table (k=31) on one "
+                     "MI355X, HIP-event ms", "value": round(pend["bases_mask_ms"] + pend["bases_rows_ms"], 4),
+           "unit": "ms", "n_gpus": 1, "steps": steps, "warmup": args.warmup, "higher_is_better": False,
+           "dtype": "u64 keys, u32 staged counts", "data": "synthetic (BASELINE configs[1] reads, device-resident)",
+           "config": {"workload": f"count_intervals: {nreads} reads ({len(batch) - nreads} bases) counted, then their "
+                                  "intervals (lo=2 in bases and in slots; lo=hi=0) and their solid runs taken from the "
+                                  "same device batch", "k": k, "intervals": rows, "distinct": int(distinct),
+                      "repeats": repeats},
+           "pending": pend, "dense": side("dense"), "repeats": reps}
+    with open(os.path.join(ROOT, "profiles", "count_intervals.jsonl"), "a") as f:
+        f.write(json.dumps(out) + "\n")
+    return out
+
+
 def wl_count_quantiles(args):
     """Per-read count quantiles (the median alone, then four quantiles) beside
     okm_read_depths_device over the same batch in the same process: the C2
@@ -1369,7 +1462,7 @@ def wl_classify(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth", "compare", "combine", "solid_runs", "count_quantiles"],
+    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth", "compare", "combine", "solid_runs", "count_quantiles", "count_intervals"],
                     required=True)
     ap.add_argument("--no-ref", action="store_true", help="c3: skip the one-GPU reference table")
     ap.add_argument("--c3-reads", type=int, default=C3_READS,
@@ -1394,7 +1487,8 @@ def main():
     c5 = wl_c5_dist if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.loopback else wl_c5
     out = {"query": wl_query, "build": wl_build, "wide": wl_wide, "classify": wl_classify,
            "c5": c5, "c3": wl_c3_loop, "histogram": wl_histogram, "lookup": wl_lookup, "depth": wl_depth,
-           "compare": wl_compare, "combine": wl_combine, "solid_runs": wl_solid_runs, "count_quantiles": wl_count_quantiles}[args.workload](args)
+           "compare": wl_compare, "combine": wl_combine, "solid_runs": wl_solid_runs, "count_quantiles": wl_count_quantiles,
+           "count_intervals": wl_count_intervals}[args.workload](args)
     if out is not None:
         print(json.dumps(out), flush=True)
 
