@@ -418,6 +418,32 @@ typedef struct okm_count_compare {
 okm_status okm_compare_counts(okm_ctx *a, okm_ctx *b, uint64_t min_count_a, uint64_t min_count_b,
                               okm_count_compare *out);
 
+/* The joint count spectrum of two counted tables -- the matrix that KAT `comp`
+ * prints and Merqury's spectra-cn / spectra-asm plot; an extension.  "Kept"
+ * means what it means for okm_compare_counts: an entry whose count is at least
+ * its side's min_count (0 behaves as 1; every threshold up to 2^64 - 1 is
+ * exact); an entry that is not kept is absent from its side.  For every key
+ * kept on at least one side, with ca / cb its count on that side (0 where it
+ * is not kept):
+ *   matrix[min(ca, bins_a - 1) * bins_b + min(cb, bins_b - 1)] += 1
+ * So column 0 is what only a keeps, row 0 what only b keeps, matrix[0][0] is
+ * always 0, the last row and the last column take every count at or past
+ * their label (like the last bin of okm_count_histogram), the row sums are
+ * a's kept histogram, the column sums b's, and the sum of all cells is the
+ * size of the union.  2 <= bins_a, bins_b <= 65536 and bins_a * bins_b <= 2^22,
+ * else OKM_E_ARG.  a == b is allowed (all mass on the clamped diagonal); an
+ * empty side leaves only the other's row or column, two empty tables zeros.
+ * A set-mode context on either side: OKM_E_STATE.  Contexts of different k,
+ * width (k > 32 or not) or device, or a null argument: OKM_E_ARG.  Both
+ * contexts are counted first if batches are pending.  Read-only, like
+ * okm_compare_counts: both tables stay where and as they lie (nothing is
+ * gathered, a host-resident table goes up in slices) and are merged once; the
+ * matrix is built on the device and comes down in one copy.  On failure the
+ * matrix is not defined and both contexts stay as they were. */
+okm_status okm_compare_histogram(okm_ctx *a, okm_ctx *b, uint64_t min_count_a, uint64_t min_count_b,
+                                 uint64_t *matrix /* host, bins_a * bins_b, row-major [ca][cb] */,
+                                 uint64_t bins_a, uint64_t bins_b);
+
 /* Two counted tables combined into a third -- `kmc_tools simple` union /
  * intersect / kmers_subtract / counters_subtract, meryl union-sum / intersect /
  * difference / subtract; an extension.  "Kept" means what it means for

@@ -220,7 +220,7 @@ static const char *kVersion = "orion-kmer 0.1.0";
 
 static void print_help(const std::string &cmd) {
     if (cmd == "count")
-        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n      --depth <FASTX>              Take the k-mer depth of every record of FASTX in the whole table (extension)\n      --depth-output <FILE>        Where --depth writes id<TAB>windows<TAB>present<TAB>solid<TAB>sum<TAB>min<TAB>max, in input order\n      --depth-min-count <N>        A window is solid when its k-mer's count is at least N [default: 2]\n      --solid-runs <FASTX>         Find the solid runs of every record of FASTX in the whole table: where its solid k-mers lie (extension)\n      --solid-runs-output <FILE>   Where --solid-runs writes id<TAB>slots<TAB>solid<TAB>run_start<TAB>run_len<TAB>lead<TAB>trail, in input order\n      --solid-runs-min-count <N>   A slot is solid when its k-mer's count is at least N [default: 2]\n      --quantiles <FASTX>          Per record of FASTX: quantiles of its k-mers' counts in the table, the median by default (extension)\n      --quantiles-output <FILE>    Where --quantiles writes id<TAB>windows<TAB>one value per quantile, in input order\n      --quantiles-at <A/B,...>     Up to 4 fractions: the sorted counts' element at index windows * A / B [default: 1/2]\n      --intervals <FASTX>          Per record of FASTX: the stretches whose k-mers' counts in the table lie in a range, as BED (extension)\n      --intervals-output <FILE>    Where --intervals writes id<TAB>start<TAB>end, 0-based and half-open, in input order\n      --intervals-min-count <N>    The range's lower end; 0 selects the k-mers the table lacks [default: 2]\n      --intervals-max-count <N>    The range's upper end [default: unbounded]\n      --intervals-slots            Intervals of window starts, not of the bases the windows cover\n      --compare <FASTX>          Count FASTX as a second table (same k) and compare the two tables with their counts (extension)\n      --compare-output <FILE>      Where --compare writes field<TAB>value: the shared k-mers, their counts, Jaccard, weighted Jaccard, Bray-Curtis\n      --compare-min-count <N>      Minimum count of a k-mer of the --compare table (--min-count: of the first table) [default: 1]\n      --combine <FASTX>            Count FASTX as a second table (same k) and combine the two tables into a third (extension)\n      --combine-op <OP>            union, intersect, intersect_left, difference or subtract (the first table is the left one)\n      --combine-output <FILE>      Where --combine writes the combined table as KMER<TAB>COUNT lines\n      --combine-min-count <N>      Minimum count of a k-mer of the --combine table (--min-count: of the first table) [default: 1]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
+        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n      --depth <FASTX>              Take the k-mer depth of every record of FASTX in the whole table (extension)\n      --depth-output <FILE>        Where --depth writes id<TAB>windows<TAB>present<TAB>solid<TAB>sum<TAB>min<TAB>max, in input order\n      --depth-min-count <N>        A window is solid when its k-mer's count is at least N [default: 2]\n      --solid-runs <FASTX>         Find the solid runs of every record of FASTX in the whole table: where its solid k-mers lie (extension)\n      --solid-runs-output <FILE>   Where --solid-runs writes id<TAB>slots<TAB>solid<TAB>run_start<TAB>run_len<TAB>lead<TAB>trail, in input order\n      --solid-runs-min-count <N>   A slot is solid when its k-mer's count is at least N [default: 2]\n      --quantiles <FASTX>          Per record of FASTX: quantiles of its k-mers' counts in the table, the median by default (extension)\n      --quantiles-output <FILE>    Where --quantiles writes id<TAB>windows<TAB>one value per quantile, in input order\n      --quantiles-at <A/B,...>     Up to 4 fractions: the sorted counts' element at index windows * A / B [default: 1/2]\n      --intervals <FASTX>          Per record of FASTX: the stretches whose k-mers' counts in the table lie in a range, as BED (extension)\n      --intervals-output <FILE>    Where --intervals writes id<TAB>start<TAB>end, 0-based and half-open, in input order\n      --intervals-min-count <N>    The range's lower end; 0 selects the k-mers the table lacks [default: 2]\n      --intervals-max-count <N>    The range's upper end [default: unbounded]\n      --intervals-slots            Intervals of window starts, not of the bases the windows cover\n      --compare <FASTX>          Count FASTX as a second table (same k) and compare the two tables with their counts (extension)\n      --compare-output <FILE>      Where --compare writes field<TAB>value: the shared k-mers, their counts, Jaccard, weighted Jaccard, Bray-Curtis\n      --compare-min-count <N>      Minimum count of a k-mer of the --compare table (--min-count: of the first table) [default: 1]\n      --compare-matrix <FILE>      Where --compare also writes the joint count spectrum as count_a<TAB>count_b<TAB>kmers lines (KAT comp; extension)\n      --compare-matrix-bins <A>,<B>  Rows and columns of the --compare-matrix; the last of each takes every larger count [default: 1001,1001]\n      --combine <FASTX>            Count FASTX as a second table (same k) and combine the two tables into a third (extension)\n      --combine-op <OP>            union, intersect, intersect_left, difference or subtract (the first table is the left one)\n      --combine-output <FILE>      Where --combine writes the combined table as KMER<TAB>COUNT lines\n      --combine-min-count <N>      Minimum count of a k-mer of the --combine table (--min-count: of the first table) [default: 1]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
     else if (cmd == "build")
         printf("Build a unique k-mer database from genome assemblies\n\nUsage: orion-kmer build [OPTIONS] --kmer-size <KMER_SIZE> --genomes <GENOME_FILES>... --output-file <OUTPUT_FILE>\n");
     else if (cmd == "compare")
@@ -492,13 +492,16 @@ static int write_intervals(okm_ctx *ctx, okm_reader *r, const std::string &path,
 // first table's (one GPU), okm_compare_counts of the two, and field<TAB>value
 // lines: the eight fields, then the ratios that follow from them, printed with
 // four decimals as the reference prints its floats (0 where nothing is kept).
+// With --compare-matrix, okm_compare_histogram of the same two tables at the
+// same thresholds follows, written as count_a<TAB>count_b<TAB>kmers lines.
 struct CompareCtx {
     okm_ctx *c = nullptr;
     ~CompareCtx() { okm_destroy(c); }
 };
 
 static int write_compare(okm_ctx *first, uint8_t k, bool wide, const std::string &path, const std::string &out_path,
-                         uint64_t min_a, uint64_t min_b) {
+                         uint64_t min_a, uint64_t min_b, const std::string &matrix_path, uint64_t bins_a,
+                         uint64_t bins_b) {
     CompareCtx second;
     int rc = open_engine(&second.c, k, (okm_mode)(OKM_MODE_COUNT | (wide ? OKM_MODE_WIDE : 0)));
     if (rc) return rc;
@@ -525,6 +528,18 @@ static int write_compare(okm_ctx *first, uint8_t k, bool wide, const std::string
     }
     if (okm_write_file(out_path.c_str(), reinterpret_cast<const uint8_t *>(lines.data()), lines.size()) != OKM_OK)
         return die("Failed to get output writer for compare output file: " + dbg_path(out_path));
+    if (matrix_path.empty()) return 0;
+    // --compare-matrix: the joint spectrum of the same two tables, the non-zero cells in row-major order
+    std::vector<uint64_t> m(bins_a * bins_b);
+    if (okm_compare_histogram(first, second.c, min_a, min_b, m.data(), bins_a, bins_b) != OKM_OK)
+        return die("GPU engine failure while taking the joint count spectrum: " + err_detail());
+    lines.clear();
+    for (uint64_t ca = 0; ca < bins_a; ++ca)
+        for (uint64_t cb = 0; cb < bins_b; ++cb)
+            if (const uint64_t v = m[ca * bins_b + cb])
+                lines += std::to_string(ca) + '\t' + std::to_string(cb) + '\t' + std::to_string(v) + '\n';
+    if (okm_write_file(matrix_path.c_str(), reinterpret_cast<const uint8_t *>(lines.data()), lines.size()) != OKM_OK)
+        return die("Failed to get output writer for compare matrix file: " + dbg_path(matrix_path));
     return 0;
 }
 
@@ -659,6 +674,22 @@ static int run_count(const Args &a) {
         return usage_error("invalid value '" + cm + "' for '--compare-min-count <N>'");
     if (want_cmp && g_gpus != 1)
         return usage_error("the argument '--compare <FASTX>' cannot be used with '--gpus <GPUS>' other than 1");
+    // [--compare-matrix <FILE>] [--compare-matrix-bins <A>,<B>]: the joint count spectrum of the same two
+    // tables at the same thresholds, beside --compare-output (an additional output, not another one)
+    std::string cmx_path, cmx_bins;
+    const bool want_cmx = get_one(a, "compare-matrix", cmx_path), has_cmx_bins = get_one(a, "compare-matrix-bins", cmx_bins);
+    if ((want_cmx || has_cmx_bins) && !want_cmp)
+        return usage_error("the following required arguments were not provided:\n  --compare <FASTX>");
+    if (has_cmx_bins && !want_cmx)
+        return usage_error("the following required arguments were not provided:\n  --compare-matrix <FILE>");
+    uint64_t cmx_a = 1001, cmx_b = 1001;
+    if (has_cmx_bins) {
+        const size_t comma = cmx_bins.find(',');
+        if (comma == std::string::npos || !parse_u64(cmx_bins.substr(0, comma), cmx_a) ||
+            !parse_u64(cmx_bins.substr(comma + 1), cmx_b) || cmx_a < 2 || cmx_b < 2 || cmx_a > 65536 || cmx_b > 65536 ||
+            cmx_a * cmx_b > (uint64_t(1) << 22))
+            return usage_error("invalid value '" + cmx_bins + "' for '--compare-matrix-bins <A>,<B>'");
+    }
     // --combine <FASTX> --combine-op <OP> --combine-output <FILE>
     // [--combine-min-count <N>]: FASTX is counted at the same k into a second
     // table and the two are combined into a third, written as KMER<TAB>COUNT
@@ -811,7 +842,9 @@ static int run_count(const Args &a) {
         phase("intervals");
     }
     if (want_cmp) {  // both tables are merged as their counts left them
-        if ((rc = write_compare(okm_group_owner(grp, 0), k, wide, cmp_path, cmp_out, min_count, cmp_min))) return rc;
+        if ((rc = write_compare(okm_group_owner(grp, 0), k, wide, cmp_path, cmp_out, min_count, cmp_min, cmx_path, cmx_a,
+                                cmx_b)))
+            return rc;
         info("orion_kmer::commands::count", "Successfully wrote the table comparison to " + dbg_path(cmp_out));
         phase("compare");
     }
@@ -1387,6 +1420,8 @@ int main(int argc, char **argv) {
         spec.push_back({"compare", 0, true, false});
         spec.push_back({"compare-output", 0, true, false});
         spec.push_back({"compare-min-count", 0, true, false});
+        spec.push_back({"compare-matrix", 0, true, false});
+        spec.push_back({"compare-matrix-bins", 0, true, false});
         spec.push_back({"combine", 0, true, false});
         spec.push_back({"combine-op", 0, true, false});
         spec.push_back({"combine-output", 0, true, false});

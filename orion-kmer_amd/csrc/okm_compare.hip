@@ -55,10 +55,6 @@
 namespace okm {
 
 constexpr uint32_t kCmpSlots = 256, kCmpSlotWords = 16;  // the merge's result slots: one 128-B line each
-#ifndef OKM_CMP_TILE  // a build flag, for the A/B in profiles/AB_LOG.md
-#define OKM_CMP_TILE 1024
-#endif
-template <typename KT> struct CmpTileOf { static constexpr uint32_t T = OKM_CMP_TILE / (sizeof(KT) / 8); };
 
 uint32_t compare_tile(bool wide) { return wide ? CmpTileOf<K128>::T : CmpTileOf<ull>::T; }
 
@@ -337,12 +333,27 @@ void launch_compare_totals(void *stream, const TableView &v, uint64_t min_count,
 }
 
 template <typename KT>
-static void compare_tiles(hipStream_t s, const TableView &d, const TableView &sv, uint64_t min_d, uint64_t min_s,
-                          const unsigned long long *toff, CmpTile *tiles, unsigned long long *out) {
+static void compare_bounds(hipStream_t s, const TableView &d, const TableView &sv, const unsigned long long *toff,
+                           CmpTile *tiles) {
     const uint32_t T = compare_tile(sizeof(KT) == 16);
     const uint64_t max_tiles = compare_max_tiles(d.n, d.max_runs, T);
     hipLaunchKernelGGL(k_cmp_bounds<KT>, dim3((uint32_t)(max_tiles / 256 + 1)), dim3(256), 0, s, d.desc, d.n_desc, toff,
                        d.max_runs, reinterpret_cast<const KT *>(sv.first), sv.desc, sv.n_desc, T, tiles);
+}
+
+void launch_compare_bounds(void *stream, const TableView &d, const TableView &sv, bool wide,
+                           const unsigned long long *toff, CmpTile *tiles) {
+    if (wide)
+        compare_bounds<K128>((hipStream_t)stream, d, sv, toff, tiles);
+    else
+        compare_bounds<ull>((hipStream_t)stream, d, sv, toff, tiles);
+}
+
+template <typename KT>
+static void compare_tiles(hipStream_t s, const TableView &d, const TableView &sv, uint64_t min_d, uint64_t min_s,
+                          const unsigned long long *toff, CmpTile *tiles, unsigned long long *out) {
+    const uint64_t max_tiles = compare_max_tiles(d.n, d.max_runs, compare_tile(sizeof(KT) == 16));
+    compare_bounds<KT>(s, d, sv, toff, tiles);
     const dim3 g((uint32_t)max_tiles), b(kCmpBlock);
     const unsigned long long *nt = toff + d.max_runs;
 #define OKM_CMP_LAUNCH(ND, NS)                                                                                 \

@@ -3586,10 +3586,10 @@ okm_status okm_count_histogram(okm_ctx *c, uint64_t *hist, uint64_t n_bins, okm_
         const TableView v = tab.view(si);
         c->timer.begin(c->stream);
         if (tab.pending)
-            launch_hist_items(c->stream, c->pend.items, c->pend.nitems, c->pend.n_out, v.counts, v.narrow, n_bins, dh,
+            launch_hist_items(c->stream, c->pend.items, c->pend.nitems, c->pend.n_out, v.counts, v.narrow, 1, n_bins, dh,
                               dh + n_bins);
         else
-            launch_hist_dense(c->stream, v.counts, v.n, n_bins, dh, dh + n_bins);
+            launch_hist_dense(c->stream, v.counts, v.n, 1, n_bins, dh, dh + n_bins);
         c->timer.end(c->stream, "count_histogram", (v.narrow ? 4.0 : 8.0) * (double)v.n);
     }
     HIP_TRY(hipGetLastError());
@@ -3779,6 +3779,103 @@ okm_status okm_compare_counts(okm_ctx *a, okm_ctx *b, uint64_t min_count_a, uint
     out->sum_a = h[5];
     out->n_b = h[6];
     out->sum_b = h[7];
+    return OKM_OK;
+}
+
+// The joint count histogram of two tables (okm_jointhist.hip): okm_compare_counts'
+// walk over the slice pairs, with the merge binning the keys both sides keep
+// into the device matrix (slice pairs add), and each side's kept count
+// histogram (okm_hist.hip's walks, thresholded) where the compare takes its
+// totals: a's with every slice of a, b's during a's first slice.  Nothing that
+// only one table holds is attributed in the merge; k_joint_finish derives
+// column 0 and row 0 from the marginals at the end, and the matrix comes down
+// in one copy.  The scratch holds the matrix, then a's bins + 3 words (the
+// histogram's summary) and b's.
+static void joint_marginal(hipStream_t s, const TableReader &R, const TableView &v, uint64_t min_count, uint64_t bins,
+                           unsigned long long *hist) {
+    if (R.pending)
+        launch_hist_items(s, R.t->pend.items, R.t->pend.nitems, R.t->pend.n_out, v.counts, v.narrow, min_count, bins,
+                          hist, hist + bins);
+    else
+        launch_hist_dense(s, v.counts, v.n, min_count, bins, hist, hist + bins);
+}
+
+okm_status okm_compare_histogram(okm_ctx *a, okm_ctx *b, uint64_t min_count_a, uint64_t min_count_b, uint64_t *matrix,
+                                 uint64_t bins_a, uint64_t bins_b) {
+    if (!a || !b || !matrix) return fail(OKM_E_ARG, "okm_compare_histogram: null argument");
+    if (bins_a < 2 || bins_b < 2 || bins_a > 65536 || bins_b > 65536 || bins_a * bins_b > (uint64_t(1) << 22))
+        return fail(OKM_E_ARG, "okm_compare_histogram: bins " + std::to_string(bins_a) + " x " + std::to_string(bins_b) +
+                                   " are not in 2..=65536 each with a product of at most 2^22");
+    if (a->mode == OKM_MODE_SET || b->mode == OKM_MODE_SET)
+        return fail(OKM_E_STATE, "okm_compare_histogram: a set-mode context has no counts");
+    if (a->k != b->k || a->wide != b->wide)
+        return fail(OKM_E_ARG, "okm_compare_histogram: the contexts differ in k or in key width");
+    if (a->device != b->device) return fail(OKM_E_ARG, "okm_compare_histogram: the contexts are on different devices");
+    min_count_a = std::max<uint64_t>(min_count_a, 1);
+    min_count_b = std::max<uint64_t>(min_count_b, 1);
+    HIP_TRY(hipSetDevice(a->device));
+    OKM_TRY(okm_count(a, nullptr));
+    if (b != a) {
+        OKM_TRY(okm_count(b, nullptr));
+        OKM_TRY(sync(b));  // its table is read from a's stream
+    }
+    hipStream_t s = a->stream;
+    Blocks scratch(*a->pool);
+    const uint64_t cells = bins_a * bins_b, words = cells + bins_a + 3 + bins_b + 3;
+    unsigned long long *dm = nullptr;
+    OKM_TRY(scratch.get(words, &dm));
+    HIP_TRY(hipMemsetAsync(dm, 0, words * sizeof(unsigned long long), s));
+    unsigned long long *ha = dm + cells, *hb = ha + bins_a + 3;
+    const uint32_t tile = compare_tile(a->wide);
+    TableReader A(a, TableForm::Runs, tile), B(b, TableForm::Runs, tile);
+    OKM_TRY(A.prepare(scratch));
+    OKM_TRY(B.prepare(scratch));
+    const bool a_drives = a->n_res >= b->n_res;
+    const TableReader &D = a_drives ? A : B, &S = a_drives ? B : A;
+    unsigned long long *toff = nullptr, *ttmp = nullptr;
+    CmpTile *tiles = nullptr;
+    if (S.nslices) {  // (then D has entries too)
+        OKM_TRY(scratch.get((size_t)D.max_runs + 1, &toff));
+        OKM_TRY(scratch.get(scan_tmp_elems((uint64_t)D.max_runs + 1), &ttmp));
+        OKM_TRY(scratch.get(compare_max_tiles(D.sl, D.max_runs, tile), &tiles));
+    }
+    const bool has_a = A.nslices > 0, has_b = B.nslices > 0;
+    const auto cw = [](const TableView &v) { return (v.narrow ? 4.0 : 8.0) * (double)v.n; };
+    TableView va, vb;  // a's slice si, b's slice sj
+    for (uint64_t si = 0; si < std::max<uint64_t>(A.nslices, 1); ++si) {
+        for (uint64_t sj = 0; sj < std::max<uint64_t>(B.nslices, 1); ++sj) {
+            const bool a_new = has_a && sj == 0;                     // a's slice si: index it, take its marginal
+            const bool b_new = has_b && (si == 0 || B.nslices > 1);  // a device-resident b is indexed once
+            if (a_new) OKM_TRY(A.upload(s, si));
+            if (b_new) OKM_TRY(B.upload(s, sj));
+            a->timer.begin(s);
+            double bytes = 0;  // the keys and counts of both tables once, and the counts again for the marginals
+            if (a_new) {
+                A.index(s, si);
+                va = A.view(si);
+                joint_marginal(s, A, va, min_count_a, bins_a, ha);
+                bytes += 8.0 * a->kw * (double)va.n + 2 * cw(va);
+            }
+            if (b_new) {
+                B.index(s, sj);
+                vb = B.view(sj);
+            }
+            if (has_b && si == 0) {
+                joint_marginal(s, B, vb, min_count_b, bins_b, hb);
+                bytes += 8.0 * a->kw * (double)vb.n + 2 * cw(vb);
+            }
+            if (has_a && has_b)
+                launch_joint_tiles(s, a_drives ? va : vb, a_drives ? vb : va, a->wide, a_drives,
+                                   a_drives ? min_count_a : min_count_b, a_drives ? min_count_b : min_count_a, bins_a,
+                                   bins_b, toff, ttmp, tiles, dm);
+            if (si + 1 >= A.nslices && sj + 1 >= B.nslices) launch_joint_finish(s, dm, ha, hb, bins_a, bins_b);
+            a->timer.end(s, "compare_histogram", bytes);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(matrix, dm, cells * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    OKM_TRY(sync(a));
+    scratch.free_all();
     return OKM_OK;
 }
 

@@ -1,7 +1,9 @@
 // okm_hist.hip — the count histogram (abundance spectrum) of a counted table,
 // read where the table lies (okm_count_histogram): hist[min(count, n_bins - 1)]
 // += 1 per distinct key, plus the table's entries, the sum of its counts and
-// its largest count.  Only counts are read, never keys.
+// its largest count.  Only counts are read, never keys.  Both walks take a
+// threshold: an entry below min_count takes part in nothing (the histogram
+// passes 1; the joint histogram's marginals, okm_jointhist.hip, their side's).
 //
 // Binning.  A spectrum can be concentrated (all of a wave's counts in a few
 // low bins), and 64 lanes of LDS atomics then queue on a few addresses.  Each
@@ -140,7 +142,7 @@ __device__ __forceinline__ void hist_flush(HistAcc &a, uint32_t nlds, uint32_t *
 template <bool NARROW>
 __global__ __launch_bounds__(kHistBlock) void k_hist_items(const DevItem *__restrict__ items, uint32_t nitems,
                                                     const ull *__restrict__ n_out, const uint64_t *__restrict__ sc,
-                                                    uint64_t last, uint32_t nlds, ull *__restrict__ hist,
+                                                    uint64_t min_count, uint64_t last, uint32_t nlds, ull *__restrict__ hist,
                                                     ull *__restrict__ summary) {
     __shared__ uint32_t lds[kHistLds];
     HistAcc a;
@@ -183,7 +185,7 @@ __global__ __launch_bounds__(kHistBlock) void k_hist_items(const DevItem *__rest
             for (int q = 0; q < kHistFly; ++q) c[q] = !ok[q] ? 0 : NARROW ? (ull)sc32[at[q]] : (ull)sc[at[q]];
 #pragma unroll
             for (int q = 0; q < kHistFly; ++q)
-                if (ok[q]) hist_add(a, c[q], last, nlds, lds, hist);
+                if (ok[q] && c[q] >= min_count) hist_add(a, c[q], last, nlds, lds, hist);
         }
     }
     hist_flush(a, nlds, lds, hist, summary);
@@ -191,7 +193,8 @@ __global__ __launch_bounds__(kHistBlock) void k_hist_items(const DevItem *__rest
 
 // A dense table's counts[n] (a gathered, directly counted or folded table, or
 // one uploaded slice of a host-resident one): grid-stride tiles of 4 x kHistBlock.
-__global__ __launch_bounds__(kHistBlock) void k_hist_dense(const uint64_t *__restrict__ counts, uint64_t n, uint64_t last,
+__global__ __launch_bounds__(kHistBlock) void k_hist_dense(const uint64_t *__restrict__ counts, uint64_t n,
+                                                    uint64_t min_count, uint64_t last,
                                                     uint32_t nlds, ull *__restrict__ hist,
                                                     ull *__restrict__ summary) {
     __shared__ uint32_t lds[kHistLds];
@@ -206,17 +209,19 @@ __global__ __launch_bounds__(kHistBlock) void k_hist_dense(const uint64_t *__res
 #pragma unroll
             for (int q = 0; q < 4; ++q) c[q] = counts[j + kHistBlock * q];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) hist_add(a, c[q], last, nlds, lds, hist);
+            for (int q = 0; q < 4; ++q)
+                if (c[q] >= min_count) hist_add(a, c[q], last, nlds, lds, hist);
         } else {
-            for (uint64_t i = j; i < n; i += kHistBlock) hist_add(a, counts[i], last, nlds, lds, hist);
+            for (uint64_t i = j; i < n; i += kHistBlock)
+                if (counts[i] >= min_count) hist_add(a, counts[i], last, nlds, lds, hist);
         }
     }
     hist_flush(a, nlds, lds, hist, summary);
 }
 
 void launch_hist_items(void *stream, const DevItem *items, uint32_t nitems, const unsigned long long *n_out,
-                       const uint64_t *counts, bool narrow, uint64_t n_bins, unsigned long long *hist,
-                       unsigned long long *summary) {
+                       const uint64_t *counts, bool narrow, uint64_t min_count, uint64_t n_bins,
+                       unsigned long long *hist, unsigned long long *summary) {
     if (!nitems) return;
     const uint32_t nlds = (uint32_t)(n_bins < kHistLds ? n_bins : kHistLds);
     // eight items per wave or more
@@ -224,20 +229,21 @@ void launch_hist_items(void *stream, const DevItem *items, uint32_t nitems, cons
     const dim3 g(want < kHistGrid ? want : kHistGrid), b(kHistBlock);
     hipStream_t s = (hipStream_t)stream;
     if (narrow)
-        hipLaunchKernelGGL(k_hist_items<true>, g, b, 0, s, items, nitems, n_out, counts, n_bins - 1, nlds, hist,
+        hipLaunchKernelGGL(k_hist_items<true>, g, b, 0, s, items, nitems, n_out, counts, min_count, n_bins - 1, nlds, hist,
                            summary);
     else
-        hipLaunchKernelGGL(k_hist_items<false>, g, b, 0, s, items, nitems, n_out, counts, n_bins - 1, nlds, hist,
+        hipLaunchKernelGGL(k_hist_items<false>, g, b, 0, s, items, nitems, n_out, counts, min_count, n_bins - 1, nlds, hist,
                            summary);
 }
 
-void launch_hist_dense(void *stream, const uint64_t *counts, uint64_t n, uint64_t n_bins, unsigned long long *hist,
-                       unsigned long long *summary) {
+void launch_hist_dense(void *stream, const uint64_t *counts, uint64_t n, uint64_t min_count, uint64_t n_bins,
+                       unsigned long long *hist, unsigned long long *summary) {
     if (!n) return;
     const uint32_t nlds = (uint32_t)(n_bins < kHistLds ? n_bins : kHistLds);
     const uint64_t want = (n + 4 * kHistBlock - 1) / (4 * kHistBlock);
     const dim3 g((uint32_t)(want < kHistGrid ? want : kHistGrid)), b(kHistBlock);
-    hipLaunchKernelGGL(k_hist_dense, g, b, 0, (hipStream_t)stream, counts, n, n_bins - 1, nlds, hist, summary);
+    hipLaunchKernelGGL(k_hist_dense, g, b, 0, (hipStream_t)stream, counts, n, min_count, n_bins - 1, nlds,
+                       hist, summary);
 }
 
 }  // namespace okm

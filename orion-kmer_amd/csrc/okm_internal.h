@@ -318,12 +318,14 @@ uint32_t filter_blocks(uint64_t n);
 // summary[0] += entries, [1] += sum of counts, [2] = max count.  Both
 // accumulate into what hist / summary hold (zeroed by the caller).  The items
 // form reads the pending segmented table's counts (u32 when narrow) where the
-// count kernels staged them; the dense form a flat u64 array.
+// count kernels staged them; the dense form a flat u64 array.  Only entries
+// with count >= min_count take part (1: every entry; the joint histogram's
+// marginals pass their side's threshold).
 void launch_hist_items(void *stream, const DevItem *items, uint32_t nitems, const unsigned long long *n_out,
-                       const uint64_t *counts, bool narrow, uint64_t n_bins, unsigned long long *hist,
-                       unsigned long long *summary);
-void launch_hist_dense(void *stream, const uint64_t *counts, uint64_t n, uint64_t n_bins, unsigned long long *hist,
-                       unsigned long long *summary);
+                       const uint64_t *counts, bool narrow, uint64_t min_count, uint64_t n_bins,
+                       unsigned long long *hist, unsigned long long *summary);
+void launch_hist_dense(void *stream, const uint64_t *counts, uint64_t n, uint64_t min_count, uint64_t n_bins,
+                       unsigned long long *hist, unsigned long long *summary);
 
 // A counted table as the in-place readers' kernels see it (the lookup, the
 // depth, the compare): one of two forms, both sorted by key.  The host's
@@ -397,6 +399,26 @@ void launch_compare_fold(void *stream, const unsigned long long *slots, unsigned
 // words, scan_tmp = scan_tmp_elems(d.max_runs + 1).
 void launch_compare_tile_offsets(void *stream, const TableView &d, uint32_t tile, unsigned long long *toff,
                                  unsigned long long *scan_tmp);
+// tiles[t] = tile t of d (cut at compare_tile(wide), toff as above) and the range of s under its key span.
+void launch_compare_bounds(void *stream, const TableView &d, const TableView &s, bool wide,
+                           const unsigned long long *toff, CmpTile *tiles);
+
+// Joint count histogram (okm_jointhist.hip): the matrix of okm_compare_histogram.
+// joint_corner: the low corner Ra x Rb of a bins_a x bins_b matrix that a
+// workgroup of the merge keeps in LDS (Ra * Rb <= 2048; a narrow side leaves
+// the wide one its rows).
+void joint_corner(uint64_t bins_a, uint64_t bins_b, uint32_t *ra, uint32_t *rb);
+// matrix[min(ca, bins_a - 1) * bins_b + min(cb, bins_b - 1)] += 1 per key kept
+// on both sides (count >= its side's threshold).  d drives (the larger table);
+// a_drives says which of the two is a.  Scratch as launch_compare's; matrix is
+// zeroed by the caller and any number of launches add into it.
+void launch_joint_tiles(void *stream, const TableView &d, const TableView &s, bool wide, bool a_drives, uint64_t min_d,
+                        uint64_t min_s, uint64_t bins_a, uint64_t bins_b, unsigned long long *toff,
+                        unsigned long long *scan_tmp, CmpTile *tiles, unsigned long long *matrix);
+// Column 0 and row 0 from the two kept marginals: matrix[ca][0] = hist_a[ca] -
+// the row's shared cells, matrix[0][cb] = hist_b[cb] - the column's.
+void launch_joint_finish(void *stream, unsigned long long *matrix, const unsigned long long *hist_a,
+                         const unsigned long long *hist_b, uint64_t bins_a, uint64_t bins_b);
 
 // Table combine (okm_combine.hip): two counted tables merged into a sorted
 // (key, u64 count) table; op is an okm_combine_op, d drives (the larger

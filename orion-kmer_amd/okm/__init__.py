@@ -437,6 +437,21 @@ class KmerCounter:
               "okm_compare_counts")
         return {f: int(getattr(cc, f)) for f, _ in _lib.CountCompare._fields_}
 
+    def compare_histogram(self, other: "KmerCounter", bins: Tuple[int, int] = (256, 256), min_count: int = 1,
+                          other_min_count: int = 1) -> np.ndarray:
+        """The joint count spectrum of this table (a) and other's (b), both
+        merged where they lie (okm_compare_histogram): a uint64 matrix of shape
+        bins with M[ca, cb] = distinct keys counted ca times here and cb times
+        there, over the entries with count >= min_count / other_min_count.
+        Column 0: kept here only; row 0: kept there only; the last row and
+        column take every count >= bins - 1 (KAT comp, Merqury spectra-cn)."""
+        ba, bb = (int(v) for v in bins)
+        ok = 2 <= ba <= 65536 and 2 <= bb <= 65536  # (the library refuses the rest: nothing is allocated for it)
+        m = np.zeros((ba, bb) if ok and ba * bb <= 1 << 22 else (1, 1), dtype=np.uint64)
+        check(lib().okm_compare_histogram(self.ctx, other.ctx, min_count, other_min_count, m.ctypes.data,
+                                          ba & (2 ** 64 - 1), bb & (2 ** 64 - 1)), "okm_compare_histogram")
+        return m
+
     def combine(self, other: "KmerCounter", op: str, min_count: int = 1, other_min_count: int = 1,
                 out: Optional["KmerCounter"] = None) -> "KmerCounter":
         """This table (a) and other's (b) merged where they lie into a third

@@ -191,6 +191,7 @@ PROTOTYPES = {
     "okm_lookup_counts": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_int, _P64]),
     "okm_group_lookup_counts": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, _P64]),
     "okm_compare_counts": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, POINTER(CountCompare)]),
+    "okm_compare_histogram": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint64, c_uint64]),
     "okm_combine_counts": (c_int, [c_void_p, c_void_p, c_int, c_uint64, c_uint64, c_void_p, POINTER(c_uint64)]),
     "okm_read_depths": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_uint64, c_void_p]),
     "okm_read_depths_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_uint64, c_void_p]),

@@ -6,7 +6,7 @@ against the oracle at small sizes.  Not for production use."""
 from __future__ import annotations
 
 import contextlib
-from typing import Dict, Iterator
+from typing import Dict, Iterator, Tuple
 
 from . import _lib
 
@@ -56,6 +56,18 @@ def get_knob(name: str) -> int:
 def device_in_use(counter) -> int:
     """Bytes of the counter's device arena that are allocated right now."""
     return int(_lib.load().okm_test_device_in_use(counter.ctx))
+
+
+def joint_corner(bins_a: int, bins_b: int) -> Tuple[int, int]:
+    """(Ra, Rb) of okm_jointhist.hip's joint_corner: the cells ca < Ra, cb < Rb
+    of a bins_a x bins_b joint histogram that a workgroup bins in LDS (at most
+    2048; 45 x 45, or a narrow side leaves the wide one its rows)."""
+    a, b = min(bins_a, 45), min(bins_b, 45)
+    if b < 45:
+        a = min(bins_a, 2048 // b)
+    elif a < 45:
+        b = min(bins_b, 2048 // a)
+    return a, b
 
 
 def reset_all() -> None:

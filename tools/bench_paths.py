@@ -44,6 +44,11 @@ input, warmup then timed steps bracketed by device syncs).
                      dense, against the composition used before in the same
                      process: the gather, okm_lookup_counts of all of A's keys
                      in B, and a torch reduction; results asserted equal.
+  --workload compare_histogram okm_compare_histogram of the same two tables at
+                     bins (1001, 1001) and (1001, 6), pending and dense, beside
+                     okm_compare_counts and the composition it replaces (gathers,
+                     two lookups, a 2-D bincount in torch); the line is appended
+                     to profiles/compare_histogram.jsonl.
   --workload depth   okm_read_depths_device of the configs[1] batch against its
                      own counted table, pending and then dense, and in the same
                      process the yardstick: okm_lookup_counts of 2^24 device
@@ -477,6 +482,113 @@ def wl_compare(args):
             "roofline": {"bound": "memory (both tables' keys and counts, once)", "kernel": "compare_counts (all launches)",
                          "alg_bytes_per_step": alg, "achieved": round(alg / (pend["median"] * 1e-3) / 1e9, 1),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s"}}
+
+
+def wl_compare_histogram(args):
+    """okm_compare_histogram of wl_compare's two counted C2-sized tables at bins
+    (1001, 1001) and (1001, 6), both tables pending and then both dense, and
+    a against itself (all mass on the diagonal).  In the same process:
+    okm_compare_counts on the same tables (the merge's yardstick: the joint
+    histogram reads the same bytes plus each side's counts once more), and the
+    composition it replaces: both gathers, okm_lookup_counts of each table's
+    keys in the other, and a 2-D bincount in torch (wall clock, synchronised;
+    the first one pays the gathers).  The matrices are asserted equal.  The
+    line is appended to profiles/compare_histogram.jsonl."""
+    import torch
+    k, repeats, shapes = 31, 3, ((1001, 1001), (1001, 6))
+    steps = max(args.steps, 5)
+    bufs = []
+    for seed in (2, 12):
+        b = okm.synth_reads(READS, READ_LEN, genome_len=GENOME_BP, genome_seed=2, seed=seed, sub_rate=0.001, n_rate=0.0001)
+        bufs.append((okm.DeviceBuffer(len(b)), len(b)))
+        bufs[-1][0].upload(b)
+        del b
+
+    def stat(c, name):
+        return dict(c.kernel_stats().get(name, {"launches": 0, "total_ms": 0.0, "alg_bytes": 0.0}))
+
+    def timed(a, name, call):
+        for _ in range(args.warmup):
+            call()
+        s0 = stat(a, name)
+        for _ in range(steps):
+            got = call()
+        s1 = stat(a, name)
+        assert s1["launches"] - s0["launches"] == steps
+        return (s1["total_ms"] - s0["total_ms"]) / steps, got, (s1["alg_bytes"] - s0["alg_bytes"]) / steps
+
+    def composed(a, b, bins):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        (ak, ac, na), (bk, bc, nb) = a.result_device(), b.result_device()
+        a_in_b = torch.empty(na, dtype=torch.int64, device="cuda")
+        b_in_a = torch.empty(nb, dtype=torch.int64, device="cuda")
+        b.lookup_device(ak, na, a_in_b.data_ptr())
+        a.lookup_device(bk, nb, b_in_a.data_ptr())
+        ca = torch.as_tensor(_DevView(ac, na), device="cuda").clamp(max=bins[0] - 1)
+        cb = torch.as_tensor(_DevView(bc, nb), device="cuda").clamp(max=bins[1] - 1)
+        m = torch.bincount(ca * bins[1] + a_in_b.clamp(max=bins[1] - 1), minlength=bins[0] * bins[1])
+        m[:bins[1]] += torch.bincount(cb[b_in_a == 0], minlength=bins[1])
+        m = m.cpu().numpy().astype(np.uint64).reshape(bins)
+        return (time.perf_counter() - t) * 1e3, m
+
+    rows = []
+    with okm.KmerCounter(k) as a, okm.KmerCounter(k) as b:
+        for rep in range(repeats):
+            for c, (buf, n) in zip((a, b), bufs):
+                c.reset()
+                c.add_device_batch(buf.address, n)
+                c.count()
+                c.set_timing(True)
+            g0 = stat(a, "compact_items")["launches"] + stat(b, "compact_items")["launches"]
+            row, got = {}, {}
+            row["compare_counts_pending_ms"], _, row["compare_counts_alg_bytes"] = timed(a, "compare_counts", lambda: a.compare_counts(b))
+            for bins in shapes:
+                tag = "%dx%d" % bins
+                row[tag + "_pending_ms"], got[bins], row[tag + "_alg_bytes"] = timed(
+                    a, "compare_histogram", lambda: a.compare_histogram(b, bins))
+            row["1001x1001_self_pending_ms"], self_m, _ = timed(a, "compare_histogram", lambda: a.compare_histogram(a, shapes[0]))
+            assert stat(a, "compact_items")["launches"] + stat(b, "compact_items")["launches"] == g0, "the histogram gathered"
+            assert int(self_m.sum()) == int(np.trace(self_m)) == a.count()
+            for bins in shapes:  # (the first composition pays both gathers and leaves both tables dense)
+                tag = "%dx%d" % bins
+                row[tag + "_before_wall_ms"], ref = composed(a, b, bins)
+                assert np.array_equal(got[bins], ref), tag
+            row["compare_counts_dense_ms"], _, _ = timed(a, "compare_counts", lambda: a.compare_counts(b))
+            for bins in shapes:
+                tag = "%dx%d" % bins
+                row[tag + "_dense_ms"], dgot, _ = timed(a, "compare_histogram", lambda: a.compare_histogram(b, bins))
+                assert np.array_equal(dgot, got[bins]), tag
+            rows.append(row)
+            log(json.dumps(row))
+    for buf, _ in bufs:
+        buf.free()
+
+    def col(name):
+        v = sorted(r[name] for r in rows)
+        return {"median": round(v[len(v) // 2], 4), "min": round(v[0], 4), "max": round(v[-1], 4)}
+
+    out = {"metric": "joint count spectrum of two counted C2 tables (k=31) where they lie on one MI355X, HIP-event ms",
+           "value": col("1001x1001_pending_ms")["median"], "unit": "ms", "n_gpus": 1, "steps": steps, "warmup": args.warmup,
+           "higher_is_better": False, "dtype": "u64 keys, u32 staged counts, u32 LDS bins, u64 matrix",
+           "data": "synthetic (BASELINE configs[1] reads and a second read seed of the same genome, device-resident)",
+           "config": {"workload": "compare_histogram: 2 x 3,355,443 x 150 bp reads counted into two tables", "k": k,
+                      "repeats": repeats, "union": int(got[shapes[0]].sum()), "shared": int(got[shapes[0]][1:, 1:].sum())},
+           "compare_counts": {"pending_ms": col("compare_counts_pending_ms"), "dense_ms": col("compare_counts_dense_ms")},
+           "self_1001x1001_pending_ms": col("1001x1001_self_pending_ms"), "repeats": rows}
+    for bins in shapes:
+        tag = "%dx%d" % bins
+        pend, dense = col(tag + "_pending_ms"), col(tag + "_dense_ms")
+        # (rows[0]'s first composition pays the gathers; the later ones find the tables dense)
+        out[tag] = {"pending_ms": pend, "dense_ms": dense, "before_wall_ms": col(tag + "_before_wall_ms"),
+                    "over_compare_counts_pending": round(pend["median"] / col("compare_counts_pending_ms")["median"], 4),
+                    "over_compare_counts_dense": round(dense["median"] / col("compare_counts_dense_ms")["median"], 4),
+                    "over_before_wall": round(pend["median"] / col(tag + "_before_wall_ms")["median"], 4),
+                    "alg_bytes_per_step": rows[0][tag + "_alg_bytes"]}
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "compare_histogram.jsonl"), "a") as f:
+        f.write(json.dumps(out) + "\n")
+    return out
 
 
 def wl_combine(args):
@@ -1462,7 +1574,7 @@ def wl_classify(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth", "compare", "combine", "solid_runs", "count_quantiles", "count_intervals"],
+    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth", "compare", "compare_histogram", "combine", "solid_runs", "count_quantiles", "count_intervals"],
                     required=True)
     ap.add_argument("--no-ref", action="store_true", help="c3: skip the one-GPU reference table")
     ap.add_argument("--c3-reads", type=int, default=C3_READS,
@@ -1487,7 +1599,7 @@ def main():
     c5 = wl_c5_dist if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.loopback else wl_c5
     out = {"query": wl_query, "build": wl_build, "wide": wl_wide, "classify": wl_classify,
            "c5": c5, "c3": wl_c3_loop, "histogram": wl_histogram, "lookup": wl_lookup, "depth": wl_depth,
-           "compare": wl_compare, "combine": wl_combine, "solid_runs": wl_solid_runs, "count_quantiles": wl_count_quantiles,
+           "compare": wl_compare, "compare_histogram": wl_compare_histogram, "combine": wl_combine, "solid_runs": wl_solid_runs, "count_quantiles": wl_count_quantiles,
            "count_intervals": wl_count_intervals}[args.workload](args)
     if out is not None:
         print(json.dumps(out), flush=True)
