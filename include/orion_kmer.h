@@ -129,6 +129,23 @@ okm_status okm_add_batch(okm_ctx *ctx, const uint8_t *seq, const uint64_t *offse
  * the buffer afterwards.  This is the zero-copy hot path. */
 okm_status okm_add_batch_device(okm_ctx *ctx, const uint8_t *d_seq, uint64_t n_bytes);
 
+/* Plain (uncompressed) FASTA or FASTQ text, format by its first byte as okm_reader_open does: parsed on the
+ * device (no host record walk, no host normalisation) and appended like okm_add_batch(normalized = 0).
+ * The text is a byte classification by line and a stream compaction there: FASTQ keeps its sequence
+ * lines, FASTA its non-header lines without whitespace, each record ends in OKM_RECORD_SEPARATOR.
+ * It goes through in chunks (64 MiB), so device memory does not grow with the input; a FASTQ chunk
+ * ends at a record, a FASTA chunk anywhere.  n_bytes == 0 or a first byte that is neither '>' nor
+ * '@': OKM_E_PARSE.  Malformed FASTQ: OKM_E_RECORD with okm_parse_buffer's message; the records of
+ * earlier chunks may already have been added, and the context stays usable.  A null pointer:
+ * OKM_E_ARG.  *n_records = FASTA header lines or FASTQ records parsed.  Known limit: one FASTQ
+ * record of 2^31 bytes or more is OKM_E_ARG. */
+okm_status okm_add_text(okm_ctx *ctx, const uint8_t *text, uint64_t n_bytes, uint64_t *n_records /* may be NULL */);
+/* The same over text in DEVICE memory (any alignment; an unaligned chunk is copied to staging).  Text
+ * read in place is loaded in whole 16-B aligned granules, as okm_add_batch_device loads its batch: the
+ * up to 15 bytes behind n_bytes in the text's last granule are loaded and never looked at (a granule
+ * that begins inside a device allocation lies inside it). */
+okm_status okm_add_text_device(okm_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint64_t *n_records);
+
 /* Append (canonical key, count) pairs in DEVICE memory, e.g. partial tables
  * received from other GPUs.  Counts add (the AtomicUsize fetch_add of
  * count.rs:31-34 generalised to a weight). */
@@ -756,6 +773,8 @@ okm_status okm_reader_ids(const okm_reader *r, const uint8_t **ids, const uint64
 okm_status okm_reader_next(okm_reader *r, uint64_t max_bytes, const uint8_t **seq,
                            const uint64_t **offsets, uint64_t *n_records);
 uint64_t okm_reader_records(const okm_reader *r);
+/* The reader's whole decompressed text (valid until okm_reader_close), so a C-ABI-only host can hand it over. */
+okm_status okm_reader_text(const okm_reader *r, const uint8_t **text, uint64_t *n_bytes);
 void okm_reader_close(okm_reader *r);
 /* Parse a whole in-memory FASTA/FASTQ buffer (after sniffing compression). */
 okm_status okm_parse_buffer(const uint8_t *data, uint64_t n, uint8_t **seq, uint64_t **offsets,

@@ -77,7 +77,8 @@ typedef enum okm_test_knob {
      * okm_lookup_counts, okm_read_depths): entries per uploaded slice instead of 2^26 */
     OKM_TEST_HIST_SLICE = 19,
     /* okm_read_depths: bytes of packed records per uploaded chunk instead of
-     * 32 MiB (a chunk holds whole records, at least one) */
+     * 32 MiB (a chunk holds whole records, at least one); okm_add_text: bytes
+     * of text per chunk instead of 64 MiB */
     OKM_TEST_DEPTH_CHUNK = 20,
     OKM_TEST_KNOBS = 21
 } okm_test_knob;

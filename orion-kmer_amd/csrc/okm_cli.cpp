@@ -220,7 +220,7 @@ static const char *kVersion = "orion-kmer 0.1.0";
 
 static void print_help(const std::string &cmd) {
     if (cmd == "count")
-        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n      --depth <FASTX>              Take the k-mer depth of every record of FASTX in the whole table (extension)\n      --depth-output <FILE>        Where --depth writes id<TAB>windows<TAB>present<TAB>solid<TAB>sum<TAB>min<TAB>max, in input order\n      --depth-min-count <N>        A window is solid when its k-mer's count is at least N [default: 2]\n      --solid-runs <FASTX>         Find the solid runs of every record of FASTX in the whole table: where its solid k-mers lie (extension)\n      --solid-runs-output <FILE>   Where --solid-runs writes id<TAB>slots<TAB>solid<TAB>run_start<TAB>run_len<TAB>lead<TAB>trail, in input order\n      --solid-runs-min-count <N>   A slot is solid when its k-mer's count is at least N [default: 2]\n      --quantiles <FASTX>          Per record of FASTX: quantiles of its k-mers' counts in the table, the median by default (extension)\n      --quantiles-output <FILE>    Where --quantiles writes id<TAB>windows<TAB>one value per quantile, in input order\n      --quantiles-at <A/B,...>     Up to 4 fractions: the sorted counts' element at index windows * A / B [default: 1/2]\n      --intervals <FASTX>          Per record of FASTX: the stretches whose k-mers' counts in the table lie in a range, as BED (extension)\n      --intervals-output <FILE>    Where --intervals writes id<TAB>start<TAB>end, 0-based and half-open, in input order\n      --intervals-min-count <N>    The range's lower end; 0 selects the k-mers the table lacks [default: 2]\n      --intervals-max-count <N>    The range's upper end [default: unbounded]\n      --intervals-slots            Intervals of window starts, not of the bases the windows cover\n      --compare <FASTX>          Count FASTX as a second table (same k) and compare the two tables with their counts (extension)\n      --compare-output <FILE>      Where --compare writes field<TAB>value: the shared k-mers, their counts, Jaccard, weighted Jaccard, Bray-Curtis\n      --compare-min-count <N>      Minimum count of a k-mer of the --compare table (--min-count: of the first table) [default: 1]\n      --compare-matrix <FILE>      Where --compare also writes the joint count spectrum as count_a<TAB>count_b<TAB>kmers lines (KAT comp; extension)\n      --compare-matrix-bins <A>,<B>  Rows and columns of the --compare-matrix; the last of each takes every larger count [default: 1001,1001]\n      --combine <FASTX>            Count FASTX as a second table (same k) and combine the two tables into a third (extension)\n      --combine-op <OP>            union, intersect, intersect_left, difference or subtract (the first table is the left one)\n      --combine-output <FILE>      Where --combine writes the combined table as KMER<TAB>COUNT lines\n      --combine-min-count <N>      Minimum count of a k-mer of the --combine table (--min-count: of the first table) [default: 1]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
+        printf("Count k-mers in FASTA/FASTQ files\n\nUsage: orion-kmer count [OPTIONS] --kmer-size <KMER_SIZE> --input-files <INPUT_FILES>... --output-file <OUTPUT_FILE>\n\nOptions:\n  -k, --kmer-size <KMER_SIZE>      The length of the k-mer\n  -i, --input-files <INPUT_FILES>...  One or more input FASTA/FASTQ files. Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for k-mer counts (kmer<TAB>count)\n  -m, --min-count <MIN_COUNT>      Minimum count to report a k-mer [default: 1]\n      --wide                       Allow k up to 64 (two-u64 keys; extension, not in the reference)\n      --histogram <FILE>           Also write the count histogram of the whole table (count<TAB>k-mers; extension)\n      --histogram-max <N>          Highest histogram bin; larger counts are lumped into it [default: 10000]\n      --lookup <FILE>              Look up the k-mers listed in FILE (one per line; '>' lines skipped) in the whole table (extension)\n      --lookup-output <FILE>       Where --lookup writes kmer<TAB>count, in input order (0: absent)\n      --depth <FASTX>              Take the k-mer depth of every record of FASTX in the whole table (extension)\n      --depth-output <FILE>        Where --depth writes id<TAB>windows<TAB>present<TAB>solid<TAB>sum<TAB>min<TAB>max, in input order\n      --depth-min-count <N>        A window is solid when its k-mer's count is at least N [default: 2]\n      --solid-runs <FASTX>         Find the solid runs of every record of FASTX in the whole table: where its solid k-mers lie (extension)\n      --solid-runs-output <FILE>   Where --solid-runs writes id<TAB>slots<TAB>solid<TAB>run_start<TAB>run_len<TAB>lead<TAB>trail, in input order\n      --solid-runs-min-count <N>   A slot is solid when its k-mer's count is at least N [default: 2]\n      --quantiles <FASTX>          Per record of FASTX: quantiles of its k-mers' counts in the table, the median by default (extension)\n      --quantiles-output <FILE>    Where --quantiles writes id<TAB>windows<TAB>one value per quantile, in input order\n      --quantiles-at <A/B,...>     Up to 4 fractions: the sorted counts' element at index windows * A / B [default: 1/2]\n      --intervals <FASTX>          Per record of FASTX: the stretches whose k-mers' counts in the table lie in a range, as BED (extension)\n      --intervals-output <FILE>    Where --intervals writes id<TAB>start<TAB>end, 0-based and half-open, in input order\n      --intervals-min-count <N>    The range's lower end; 0 selects the k-mers the table lacks [default: 2]\n      --intervals-max-count <N>    The range's upper end [default: unbounded]\n      --intervals-slots            Intervals of window starts, not of the bases the windows cover\n      --compare <FASTX>          Count FASTX as a second table (same k) and compare the two tables with their counts (extension)\n      --compare-output <FILE>      Where --compare writes field<TAB>value: the shared k-mers, their counts, Jaccard, weighted Jaccard, Bray-Curtis\n      --compare-min-count <N>      Minimum count of a k-mer of the --compare table (--min-count: of the first table) [default: 1]\n      --compare-matrix <FILE>      Where --compare also writes the joint count spectrum as count_a<TAB>count_b<TAB>kmers lines (KAT comp; extension)\n      --compare-matrix-bins <A>,<B>  Rows and columns of the --compare-matrix; the last of each takes every larger count [default: 1001,1001]\n      --combine <FASTX>            Count FASTX as a second table (same k) and combine the two tables into a third (extension)\n      --combine-op <OP>            union, intersect, intersect_left, difference or subtract (the first table is the left one)\n      --combine-output <FILE>      Where --combine writes the combined table as KMER<TAB>COUNT lines\n      --combine-min-count <N>      Minimum count of a k-mer of the --combine table (--min-count: of the first table) [default: 1]\n  -t, --threads <THREADS>          Number of threads to use (0 for all logical cores) [default: 0]\n  -v, --verbose...                 Verbosity level (e.g., -v, -vv)\n      --device <DEVICE>            GPU ordinal (MI355X engine) [default: 0]\n      --gpus <GPUS>                Count on this many GPUs of the node, one table over RCCL (0: all) [default: 1]\n      --device-parse               Parse the FASTA/FASTQ text on the GPU instead of on the host threads (one GPU; extension)\n  -h, --help                       Print help\n  -V, --version                    Print version\n");
     else if (cmd == "build")
         printf("Build a unique k-mer database from genome assemblies\n\nUsage: orion-kmer build [OPTIONS] --kmer-size <KMER_SIZE> --genomes <GENOME_FILES>... --output-file <OUTPUT_FILE>\n");
     else if (cmd == "compare")
@@ -351,6 +351,37 @@ static int feed_file_group(AsyncGroup &ag, const std::string &path, const char *
     }
     info("orion_kmer::commands", "Finished processing " + std::to_string(okm_reader_records(r)) + " records from " + path);
     okm_reader_close(r);
+    return 0;
+}
+
+// feed_file_group with --device-parse: the reader opens and inflates the file
+// as above, and its whole text goes to the (single) GPU's context, which
+// parses it there; the messages are the host path's.
+static int feed_file_text(AsyncGroup &ag, const std::string &path, const char *open_ctx) {
+    okm_reader *r = nullptr;
+    okm_status s = okm_reader_open(&r, path.c_str(), 1);
+    if (s == OKM_E_IO) return die(std::string(open_ctx) + path);
+    if (s != OKM_OK) return die("Failed to parse FASTA/Q content from: " + path);
+    info("orion_kmer::commands", "Processing records from " + path + "...");
+    okm_group *g = ag.get();
+    if (!g) {  // no engine: the host path's message for this file, which parses its first batch before it asks
+        const uint8_t *seq;
+        const uint64_t *off;
+        uint64_t nrec;
+        s = okm_reader_next(r, 128ull << 20, &seq, &off, &nrec);
+        okm_reader_close(r);
+        return s != OKM_OK ? die("Error reading record from " + path) : engine_error(ag);
+    }
+    const uint8_t *text = nullptr;
+    uint64_t n = 0, records = 0;
+    s = okm_reader_text(r, &text, &n);
+    if (s == OKM_OK) s = okm_add_text(okm_group_owner(g, 0), text, n, &records);
+    const std::string why = s == OKM_OK ? std::string() : err_detail();
+    okm_reader_close(r);
+    if (s == OKM_E_PARSE) return die("Failed to parse FASTA/Q content from: " + path);
+    if (s == OKM_E_RECORD) return die("Error reading record from " + path);
+    if (s != OKM_OK) return die("GPU engine failure on " + path + ": " + why);
+    info("orion_kmer::commands", "Finished processing " + std::to_string(records) + " records from " + path);
     return 0;
 }
 
@@ -578,6 +609,10 @@ static int run_count(const Args &a) {
     uint64_t min_count = 1;
     if (get_one(a, "min-count", ms) && !parse_u64(ms, min_count))
         return usage_error("invalid value '" + ms + "' for '--min-count <MIN_COUNT>'");
+    // --device-parse: the input's text is parsed on the GPU (okm_add_text), one GPU
+    const bool device_parse = !get_all(a, "device-parse").empty();
+    if (device_parse && g_gpus != 1)
+        return usage_error("the argument '--device-parse' cannot be used with '--gpus <GPUS>' other than 1");
     // --histogram <FILE>: the count histogram of the WHOLE table (--min-count
     // does not apply), counts above --histogram-max lumped into its bin (an
     // extension; jellyfish histo's default high bin)
@@ -763,7 +798,8 @@ static int run_count(const Args &a) {
     ag.start(k, (okm_mode)(OKM_MODE_COUNT | (wide ? OKM_MODE_WIDE : 0)));
     for (auto &p : inputs) {
         info("orion_kmer::commands::count", "Processing file: " + p);
-        if ((rc = feed_file_group(ag, p, "Failed to get input reader for file: "))) return rc;
+        const char *open_ctx = "Failed to get input reader for file: ";
+        if ((rc = device_parse ? feed_file_text(ag, p, open_ctx) : feed_file_group(ag, p, open_ctx))) return rc;
     }
     phase("input parsed");
     okm_group *grp = ag.get();
@@ -1399,6 +1435,7 @@ int main(int argc, char **argv) {
         spec.push_back({"min-count", 'm', true, false});
         spec.push_back({"wide", 0, false, false});
         spec.push_back({"gpus", 0, true, false});
+        spec.push_back({"device-parse", 0, false, false});
         spec.push_back({"histogram", 0, true, false});
         spec.push_back({"histogram-max", 0, true, false});
         spec.push_back({"lookup", 0, true, false});

@@ -32,6 +32,7 @@
 #include "okm_arena.h"
 #include "okm_hip_try.h"
 #include "okm_internal.h"
+#include "okm_io.h"
 #include "okm_key.h"
 #include "orion_kmer_testing.h"
 
@@ -487,7 +488,9 @@ struct Run {
 using namespace okm;
 
 static const size_t kHpinBytes = size_t(4) << 20;
-static const size_t kHresWords = 8192;  // [0, 4096): L1 readback (3 nb + 2 words, nb <= 1024); [4096, 4112): count readback
+// [0, 4096): L1 readback (3 nb + 2 words, nb <= 1024); [4096, 4112): count readback;
+// the last 32 words: okm_add_text's chunk status, output tail and carried bytes (TextCall::hw)
+static const size_t kHresWords = 8192;
 static const size_t kHresCount = 4096;
 
 struct okm_ctx {
@@ -3265,6 +3268,292 @@ okm_status okm_add_batch_device(okm_ctx *c, const uint8_t *d_seq, uint64_t n_byt
         return l1_batch_or_spill(c, c->staging, n_bytes);
     }
     return l1_batch_or_spill(c, d_seq, n_bytes);
+}
+
+// okm_add_text[_device]: plain FASTA/FASTQ text parsed on the device
+// (okm_text.hip), chunk by chunk.  Per chunk:
+//   FASTQ  k_text_lines  k_text_scan  | newlines read back |  k_text_keep (count, newline index)
+//          k_text_check  | status and the end E of the last whole record read back |
+//          k_text_scan  k_text_keep (compact [0, E))  | output size read back |  l1_batch
+//   FASTA  k_text_lines  k_text_scan  k_text_keep (count)  k_text_scan  k_text_keep (compact)
+//          k_text_tail  | one read-back |  l1_batch
+// A FASTQ chunk is cut at E: [E, end) is presented again in front of the next
+// chunk, and a chunk without a whole record is presented again at twice its
+// size.  A FASTA chunk is cut anywhere; what crosses the cut is two bits (at a
+// line start, inside a header) and the last k - 1 kept bytes since the last
+// separator, which go in front of the next chunk's output -- l1_batch_or_spill's
+// rule for the halves of a batch.  Device memory: the chunk's text (taken by the
+// first chunk that cannot be read in place: host text, or a device chunk that
+// does not start on a 16-B boundary), its output, a tile's four words per
+// 16 KiB, and the newline index at the chunk's own number of newlines.
+constexpr uint64_t kTextChunk = uint64_t(64) << 20;
+// A FASTA chunk whose output stays below this is not a batch of its own: it
+// waits in front of the next chunk's output (chunks of a few bytes would
+// otherwise leave a run each).
+constexpr uint64_t kTextMinBatch = 1024;
+
+extern "C++" {
+namespace {
+struct TextCall {
+    okm_ctx *c;
+    Blocks scratch;
+    bool fastq = false;
+    const uint8_t *host = nullptr, *dev = nullptr;  // the caller's text: exactly one is set
+    uint64_t n_all = 0, chunk = kTextChunk;
+    uint64_t cap = 0;  // bytes of text the blocks below serve
+    uint64_t *dtext = nullptr, *dout = nullptr;
+    unsigned long long *tiles = nullptr, *words = nullptr, *hw = nullptr;  // hw: pinned, 32 words
+    uint32_t *nlidx = nullptr;
+    uint64_t nl_cap = 0;
+    // host text: two pinned halves of c->pinned, one of them staged ahead
+    uint64_t half = 0, st_begin = 0, st_len = 0;
+    int st_buf = -1;
+    // what crosses a FASTA cut
+    uint32_t at_start = 1, in_header = 0;
+    uint32_t plen = 0;          // bytes in front of the chunk's output: kept but not yet added, or the carried k - 1
+    bool prefix_on_host = false;  // they are the carried bytes, in hw[24..]
+    uint64_t records = 0;
+    // hw: 32 words of the context's pinned landing area that no count or L1 read-back uses
+    explicit TextCall(okm_ctx *ctx) : c(ctx), scratch(*ctx->pool), hw(ctx->hres + kHresWords - 32) {}
+
+    okm_status reserve(uint64_t n) {
+        if (n >> 31) return fail(OKM_E_ARG, "okm_add_text: a chunk of 2^31 bytes or more (one FASTQ record that long)");
+        if (n <= cap) return OKM_OK;
+        OKM_TRY(sync(c));  // nothing in flight reads the blocks that go back
+        scratch.free_all();
+        dtext = dout = nullptr;
+        tiles = words = nullptr;
+        nlidx = nullptr;
+        nl_cap = cap = 0;
+        const uint64_t want = std::max(n, chunk);
+        OKM_TRY(scratch.get((want + kTextMinBatch + 128) / 8 + 1, &dout));
+        OKM_TRY(scratch.get(4 * text_tiles(want) + 1, &tiles));
+        OKM_TRY(scratch.get(32, &words));
+        cap = want;
+        return OKM_OK;
+    }
+    void stage(int buf, uint64_t begin, uint64_t len) {
+        uint8_t *dst = c->pinned + (uint64_t)buf * half;
+        const uint64_t piece = uint64_t(1) << 20, np = (len + piece - 1) / piece;
+        parallel_for(np, [&](size_t i) {
+            std::memcpy(dst + i * piece, host + begin + i * piece, std::min<uint64_t>(piece, len - i * piece));
+        });
+        st_buf = buf;
+        st_begin = begin;
+        st_len = len;
+    }
+    // *src = text[pos, pos + n) in device memory, 16-B aligned
+    okm_status present(uint64_t pos, uint64_t n, const uint8_t **src) {
+        if (dev && (reinterpret_cast<uintptr_t>(dev + pos) & 15u) == 0) {  // read in place
+            *src = dev + pos;
+            return OKM_OK;
+        }
+        if (!dtext) OKM_TRY(scratch.get(cap / 8 + 2, &dtext));  // taken by the first chunk that needs it
+        uint8_t *dt = reinterpret_cast<uint8_t *>(dtext);
+        if (dev) {
+            HIP_TRY(hipMemcpyAsync(dt, dev + pos, n, hipMemcpyDeviceToDevice, c->stream));
+            *src = dt;
+            return OKM_OK;
+        }
+        *src = dt;
+        const bool ahead = st_buf >= 0 && st_begin >= pos && st_begin + st_len == pos + n;
+        if (!ahead) {
+            OKM_TRY(sync(c));  // the pinned halves are free
+            OKM_TRY(ensure_pinned(c, 2 * std::max(n, chunk)));
+            half = c->pinned_cap / 2;
+            stage(0, pos, n);
+        }
+        const uint64_t left = st_begin - pos;  // a FASTQ chunk's unparsed tail, straight from the caller's memory
+        if (left) HIP_TRY(hipMemcpyAsync(dt, host + pos, left, hipMemcpyHostToDevice, c->stream));
+        if (st_len)
+            HIP_TRY(hipMemcpyAsync(dt + left, c->pinned + (uint64_t)st_buf * half, st_len, hipMemcpyHostToDevice, c->stream));
+        // the next chunk's new bytes into the other half while this one goes up
+        // (its last reader, the chunk before this one, was synchronised)
+        const uint64_t nb = pos + n, nlen = std::min(chunk, n_all - nb);
+        if (nlen) stage(st_buf ^ 1, nb, nlen);
+        else st_buf = -1;
+        return OKM_OK;
+    }
+    okm_status read_words(uint32_t first, uint32_t count) {
+        HIP_TRY(hipMemcpyAsync(hw + first, words + first, count * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                               c->stream));
+        return sync(c);
+    }
+    static okm_status record_error(uint32_t kind) {
+        switch (kind) {
+        case kTextTruncated: return fail(OKM_E_RECORD, "truncated FASTQ record");
+        case kTextNoPlus: return fail(OKM_E_RECORD, "expected '+' separator line in FASTQ record");
+        case kTextLengths: return fail(OKM_E_RECORD, "sequence and quality lengths differ");
+        default: return fail(OKM_E_RECORD, "expected '@' at the start of a FASTQ record");
+        }
+    }
+    // Is text[pos, n_all) made of CR / LF only (FASTQ: blank lines at the very end)?
+    okm_status rest_is_blank(uint64_t pos, bool *blank) {
+        if (host) {
+            uint64_t q = pos;
+            while (q < n_all && (host[q] == '\n' || host[q] == '\r')) ++q;
+            *blank = q == n_all;
+            return OKM_OK;
+        }
+        hw[7] = 0;
+        HIP_TRY(hipMemcpyAsync(words + 7, hw + 7, 8, hipMemcpyHostToDevice, c->stream));
+        launch_text_blank(c->stream, dev + pos, n_all - pos, words + 7);
+        HIP_TRY(hipGetLastError());
+        OKM_TRY(read_words(7, 1));
+        *blank = hw[7] == 0;
+        return OKM_OK;
+    }
+    // The kept bytes [0, upto) of the chunk, behind the plen carried bytes, into the table.
+    okm_status compact_and_add(const uint8_t *src, uint64_t upto, bool tail, bool last) {
+        const uint64_t nt = text_tiles(upto);
+        unsigned long long *state = tiles + text_tiles(cap), *keep = state + text_tiles(cap), *off = keep + text_tiles(cap);
+        uint8_t *out = reinterpret_cast<uint8_t *>(dout);
+        c->timer.begin(c->stream);
+        launch_text_scan(c->stream, keep, nt, plen, false, off, words + 5, nullptr);
+        c->timer.end(c->stream, "text_scan", 16.0 * (double)nt);
+        c->timer.begin(c->stream);
+        launch_text_compact(c->stream, fastq, src, upto, at_start, state, off, out, words + 2);
+        if (tail) launch_text_tail(c->stream, out, src, upto, words);
+        c->timer.end(c->stream, "text_keep", 2.0 * (double)upto);
+        HIP_TRY(hipGetLastError());
+        OKM_TRY(read_words(2, 14));
+        const uint64_t total = hw[2];
+        if (tail && !last && total < kTextMinBatch) {  // too little for a batch of its own: the next chunk's joins it
+            plen = (uint32_t)total;
+            prefix_on_host = false;
+            return OKM_OK;
+        }
+        if (total > (prefix_on_host ? plen : 0)) OKM_TRY(l1_batch_or_spill(c, out, total));
+        if (!tail) return OKM_OK;
+        // the output's last bytes since its last separator, k - 1 at most
+        const uint8_t *tb = reinterpret_cast<const uint8_t *>(hw + 8);
+        const uint32_t have = (uint32_t)std::min<uint64_t>(total, 64);
+        uint32_t keepn = 0;
+        while (keepn < have && keepn < (uint32_t)c->k - 1 && tb[63 - keepn] != '\n') ++keepn;
+        std::memmove(hw + 24, tb + 64 - keepn, keepn);
+        plen = keepn;
+        prefix_on_host = true;
+        return OKM_OK;
+    }
+    // One chunk: *used = the bytes of it that are done with; *stop: the input ends here (FASTQ's blank tail).
+    okm_status run(const uint8_t *src, uint64_t pos, uint64_t n, bool last, uint64_t *used, bool *stop) {
+        const uint64_t nt = text_tiles(n);
+        unsigned long long *sum = tiles, *state = tiles + text_tiles(cap), *keep = state + text_tiles(cap);
+        c->timer.begin(c->stream);
+        launch_text_lines(c->stream, fastq, src, n, at_start, sum);
+        c->timer.end(c->stream, "text_lines", (double)n);
+        c->timer.begin(c->stream);
+        launch_text_scan(c->stream, sum, nt, fastq ? 0 : in_header, !fastq, state, words + 4, words);
+        c->timer.end(c->stream, "text_scan", 16.0 * (double)nt);
+        HIP_TRY(hipGetLastError());
+        *stop = false;
+        if (!fastq) {
+            c->timer.begin(c->stream);
+            launch_text_keep_count(c->stream, false, src, n, at_start, state, keep, nullptr, 0);
+            c->timer.end(c->stream, "text_keep", (double)n);
+            if (plen && prefix_on_host) HIP_TRY(hipMemcpyAsync(dout, hw + 24, plen, hipMemcpyHostToDevice, c->stream));
+            OKM_TRY(compact_and_add(src, n, true, last));
+            records += hw[5] >> 32;
+            at_start = (uint32_t)(hw[3] & 1);
+            in_header = (uint32_t)(hw[4] & 1);
+            *used = n;
+            return OKM_OK;
+        }
+        OKM_TRY(read_words(4, 1));
+        const uint64_t nnl = hw[4];
+        if (nnl > nl_cap) {
+            if (nlidx) scratch.put(nlidx);  // (synchronised: nothing reads it)
+            nlidx = nullptr;
+            nl_cap = 0;
+            OKM_TRY(scratch.get(nnl + 1, &nlidx));
+            nl_cap = nnl;
+        }
+        c->timer.begin(c->stream);
+        launch_text_keep_count(c->stream, true, src, n, 1, state, keep, nlidx, nl_cap);
+        c->timer.end(c->stream, "text_keep", (double)n + 4.0 * (double)nnl);
+        c->timer.begin(c->stream);
+        launch_text_check(c->stream, src, n, nlidx, nnl, last, words);
+        c->timer.end(c->stream, "text_check", 4.0 * (double)nnl);
+        HIP_TRY(hipGetLastError());
+        OKM_TRY(read_words(0, 7));
+        uint64_t end = hw[1], nrec = hw[6];
+        if (hw[0] != ~0ull) {
+            const uint64_t r = hw[0] >> 3;
+            const uint32_t kind = (uint32_t)(hw[0] & 7);
+            if (kind != kTextBlank) return record_error(kind);
+            // a record that starts with CR / LF: the end of the input when nothing else follows
+            end = 0;
+            if (r) {
+                uint32_t at = 0;
+                HIP_TRY(hipMemcpyAsync(hw + 7, nlidx + (4 * r - 1), 4, hipMemcpyDeviceToHost, c->stream));
+                OKM_TRY(sync(c));
+                std::memcpy(&at, hw + 7, 4);
+                end = (uint64_t)at + 1;
+            }
+            bool blank = false;
+            OKM_TRY(rest_is_blank(pos + end, &blank));
+            if (!blank) return record_error(kTextNoAt);
+            nrec = r;
+            *stop = true;
+        }
+        if (end) OKM_TRY(compact_and_add(src, end, false, last));
+        records += nrec;
+        *used = end;
+        return OKM_OK;
+    }
+    okm_status all() {
+        if (const int64_t e = test_knob(OKM_TEST_DEPTH_CHUNK); e > 0) chunk = (uint64_t)e;  // tests: several chunks
+        uint64_t pos = 0, end = std::min(n_all, chunk);
+        while (pos < n_all) {
+            const uint64_t n = end - pos;
+            const bool last = end == n_all;
+            const uint8_t *src = nullptr;
+            uint64_t used = 0;
+            bool stop = false;
+            OKM_TRY(reserve(n));
+            OKM_TRY(present(pos, n, &src));
+            OKM_TRY(run(src, pos, n, last, &used, &stop));
+            if (stop || (fastq && last)) break;
+            pos += used;
+            end = std::min(n_all, end + (used ? chunk : std::max(chunk, n)));
+        }
+        return OKM_OK;
+    }
+};
+
+okm_status add_text(okm_ctx *c, const uint8_t *host, const uint8_t *dev, uint64_t n_bytes, uint64_t *n_records) {
+    if (!c) return fail(OKM_E_ARG, "null ctx");
+    if (!host && !dev) return fail(OKM_E_ARG, "okm_add_text: null text");
+    if (n_records) *n_records = 0;
+    HIP_TRY(hipSetDevice(c->device));
+    if (n_bytes == 0) return fail(OKM_E_PARSE, "empty input");
+    uint8_t first = 0;
+    if (host) first = host[0];
+    else HIP_TRY(hipMemcpy(&first, dev, 1, hipMemcpyDeviceToHost));
+    if (first != '>' && first != '@') return fail(OKM_E_PARSE, "expected '>' or '@' at the start of the input");
+    OKM_TRY(sync(c));  // pinned buffer reuse
+    OKM_TRY(before_add(c));
+    TextCall t(c);
+    t.fastq = first == '@';
+    t.host = host;
+    t.dev = dev;
+    t.n_all = n_bytes;
+    const okm_status st = t.all();
+    const std::string why = st == OKM_OK ? std::string() : g_last_error;
+    const okm_status sy = sync(c);  // the scratch goes back with nothing in flight
+    if (st != OKM_OK) return fail(st, why);
+    if (n_records) *n_records = t.records;
+    return sy;
+}
+}  // namespace
+}  // extern "C++"
+
+okm_status okm_add_text(okm_ctx *c, const uint8_t *text, uint64_t n_bytes, uint64_t *n_records) {
+    return add_text(c, text, nullptr, n_bytes, n_records);
+}
+
+okm_status okm_add_text_device(okm_ctx *c, const uint8_t *d_text, uint64_t n_bytes, uint64_t *n_records) {
+    return add_text(c, nullptr, d_text, n_bytes, n_records);
 }
 
 okm_status okm_add_pairs_device(okm_ctx *c, const uint64_t *d_keys, const uint64_t *d_counts, uint64_t n) {

@@ -314,6 +314,13 @@ okm_status okm_reader_ids(const okm_reader *r, const uint8_t **ids, const uint64
 
 uint64_t okm_reader_records(const okm_reader *r) { return r ? r->p.records : 0; }
 
+okm_status okm_reader_text(const okm_reader *r, const uint8_t **text, uint64_t *n_bytes) {
+    if (!r || !text || !n_bytes) return fail(OKM_E_ARG, "null argument");
+    *text = r->p.data.data();
+    *n_bytes = r->p.data.size();
+    return OKM_OK;
+}
+
 void okm_reader_close(okm_reader *r) { delete r; }
 
 okm_status okm_parse_buffer(const uint8_t *data, uint64_t n, uint8_t **seq, uint64_t **offsets,

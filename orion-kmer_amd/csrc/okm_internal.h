@@ -531,6 +531,42 @@ const unsigned long long *launch_interval_rows(void *stream, uint64_t n, uint64_
                                                const unsigned long long *planes, unsigned long long *tiles,
                                                uint64_t rec0, okm_count_interval *rows, uint64_t cap);
 
+// FASTA/FASTQ text to the batch layout (okm_text.hip), over one chunk of n >= 1
+// bytes of 16-B aligned text, n < 2^31.  Tile words: text_tiles(n) each.
+//   launch_text_lines       tile_sum[t]: FASTQ the tile's newlines; FASTA bit 0 a
+//                           line starts in it, bit 1 the last such line is a header
+//                           (at_start: the chunk's first byte starts a line)
+//   launch_text_scan        one workgroup: the sum (out[t] = base + in[0, t)) or,
+//                           with `state`, the header bit at each tile's first byte;
+//                           init (optional): the chunk's status words, see below
+//   launch_text_keep_count  tile_keep[t] = kept bytes | FASTA headers << 32; FASTQ
+//                           writes every newline's position to nlidx[0, nl_cap)
+//   launch_text_compact     the kept bytes to out + (tile_off[t] & 2^32 - 1);
+//                           *out_end = the end of the output
+//   launch_text_check       FASTQ records over nlidx[0, nnl): words[0] = min of
+//                           record * 8 + TextError over the failing records (~0:
+//                           none), words[1] = end of the last record looked at,
+//                           words[6] = records looked at; `last`: the text ends here
+//   launch_text_tail        words[3] = the chunk ends in '\n', bytes of words[8..15]
+//                           = the output's last 64 bytes (its end is words[2])
+//   launch_text_blank       *flag = 1 when text[0, n) holds a byte other than CR / LF
+enum TextError : uint32_t { kTextBlank = 1, kTextNoAt = 2, kTextTruncated = 3, kTextNoPlus = 4, kTextLengths = 5 };
+uint64_t text_tiles(uint64_t n_bytes);
+void launch_text_lines(void *stream, bool fastq, const uint8_t *text, uint64_t n, uint32_t at_start,
+                       unsigned long long *tile_sum);
+void launch_text_scan(void *stream, const unsigned long long *in, uint64_t nt, unsigned long long base, bool state,
+                      unsigned long long *out, unsigned long long *total, unsigned long long *init);
+void launch_text_keep_count(void *stream, bool fastq, const uint8_t *text, uint64_t n, uint32_t at_start,
+                            const unsigned long long *tile_state, unsigned long long *tile_keep, uint32_t *nlidx,
+                            uint64_t nl_cap);
+void launch_text_compact(void *stream, bool fastq, const uint8_t *text, uint64_t n, uint32_t at_start,
+                         const unsigned long long *tile_state, const unsigned long long *tile_off, uint8_t *out,
+                         unsigned long long *out_end);
+void launch_text_check(void *stream, const uint8_t *text, uint64_t n, const uint32_t *nlidx, uint64_t nnl, bool last,
+                       unsigned long long *words);
+void launch_text_tail(void *stream, const uint8_t *out, const uint8_t *text, uint64_t n, unsigned long long *words);
+void launch_text_blank(void *stream, const uint8_t *text, uint64_t n, unsigned long long *flag);
+
 // |A ∩ B| of sorted unique arrays (merge-path style binary search per element).
 void launch_intersect_count(void *stream, const uint64_t *a, uint64_t na, const uint64_t *b,
                             uint64_t nb, unsigned long long *out, bool wide);

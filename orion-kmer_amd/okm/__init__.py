@@ -360,6 +360,19 @@ class KmerCounter:
     def add_device_batch(self, d_ptr: int, nbytes: int) -> None:
         check(lib().okm_add_batch_device(self.ctx, c_void_p(d_ptr), nbytes), "okm_add_batch_device")
 
+    def add_text(self, data: bytes) -> int:
+        """Plain FASTA/FASTQ text, parsed on the device; returns the records parsed."""
+        n = c_uint64()
+        check(lib().okm_add_text(self.ctx, data, len(data), byref(n)), "okm_add_text")
+        return n.value
+
+    def add_text_device(self, tensor) -> int:
+        """The same over a uint8 tensor that lies on this counter's device."""
+        n = c_uint64()
+        check(lib().okm_add_text_device(self.ctx, c_void_p(tensor.data_ptr()), tensor.numel(), byref(n)),
+              "okm_add_text_device")
+        return n.value
+
     def add_pairs(self, keys: np.ndarray, counts: Optional[np.ndarray] = None) -> None:
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         n = keys.shape[0] if not self.wide else keys.size // 2

@@ -102,6 +102,9 @@ PROTOTYPES = {
     "okm_trim": (c_int, [c_void_p]),
     "okm_add_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int]),
     "okm_add_batch_device": (c_int, [c_void_p, c_void_p, c_uint64]),
+    "okm_add_text": (c_int, [c_void_p, c_char_p, c_uint64, _P64]),
+    "okm_add_text_device": (c_int, [c_void_p, c_void_p, c_uint64, _P64]),
+    "okm_reader_text": (c_int, [c_void_p, POINTER(c_void_p), _P64]),
     "okm_add_pairs_device": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64]),
     "okm_add_sorted_pairs_device": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64]),
     "okm_add_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64]),

@@ -73,6 +73,12 @@ input, warmup then timed steps bracketed by device syncs).
                      batch: stage 2's ratio to the solid runs' stage 2, the
                      SLOTS rows' slots asserted to add up to `solid`; the line
                      is appended to profiles/count_intervals.jsonl.
+  --workload add_text the configs[1] reads as 1 GiB of FASTQ text to the counted
+                     table, three paths alternated in one process: the host
+                     reader's batches + okm_add_batch, okm_add_text, and
+                     okm_add_text_device on resident text; the text kernels'
+                     HIP-event times and okm_add_text at other chunk sizes; the
+                     line is appended to profiles/add_text.jsonl.
 
 The CPU baseline is the C restatement (oracle/) on a bounded sample, 1 thread.
 """
@@ -1061,6 +1067,129 @@ def wl_count_quantiles(args):
     return out
 
 
+def c2_fastq_text() -> bytes:
+    """The configs[1] reads as FASTQ text (tools/make_c2_fastq.py's records, 320 B each: 1 GiB)."""
+    t, parts, step = time.time(), [], 1 << 19
+    for r0 in range(0, READS, step):
+        m = min(step, READS - r0)
+        b = okm.synth_reads(m, READ_LEN, genome_len=GENOME_BP, genome_seed=2, seed=2, first_read=r0,
+                            sub_rate=0.001, n_rate=0.0001).reshape(m, READ_LEN + 1)
+        hdr = np.frombuffer(b"".join(b"@syn.%010d\n" % i for i in range(r0, r0 + m)), np.uint8).reshape(m, 16)
+        parts.append(np.concatenate([hdr, b[:, :READ_LEN], np.tile(np.frombuffer(b"\n+\n", np.uint8), (m, 1)),
+                                     np.full((m, READ_LEN), ord("I"), np.uint8), np.full((m, 1), 10, np.uint8)],
+                                    axis=1).tobytes())
+    text = b"".join(parts)
+    log(f"C2 FASTQ text: {len(text)} bytes ({time.time() - t:.1f}s)")
+    return text
+
+
+def wl_add_text(args):
+    """The input side of count on the configs[1] reads as 1 GiB of FASTQ text, in
+    one process, the three paths alternated, each timed by the host clock from
+    the first call to the return of okm_count (which synchronises):
+      (a) the host reader: okm_reader_next batches of 256 MiB + okm_add_batch +
+          okm_count, as the CLI feeds a file; the reader is opened on the text in
+          a page-cached file, and its open (read + newline index) is timed apart
+      (b) okm_add_text of the text in host memory + okm_count
+      (c) okm_add_text_device of the text resident in device memory + okm_count
+    then the four text kernels' HIP-event times from one more (c) with the
+    engine's timer on, and (b) at other chunk sizes.  Every run's table must
+    have the same entries and instances."""
+    import ctypes
+    import tempfile
+    from okm import _lib, testing
+    lib, k, steps = _lib.load(), 31, max(args.steps, 3)
+    text = c2_fastq_text()
+    n = len(text)
+    tmp = tempfile.NamedTemporaryFile(suffix=".fastq", delete=False)
+    tmp.write(text)
+    tmp.close()
+    dbuf = okm.DeviceBuffer(n)
+    okm.check(lib.okm_memcpy_h2d(dbuf.ptr, text, n), "okm_memcpy_h2d")
+    nrec = ctypes.c_uint64()
+
+    def path_a(c):
+        r = ctypes.c_void_p()
+        t0 = time.perf_counter()
+        okm.check(lib.okm_reader_open(ctypes.byref(r), tmp.name.encode(), 0), "okm_reader_open")
+        t1 = time.perf_counter()
+        while True:
+            seq, off = ctypes.c_void_p(), ctypes.c_void_p()
+            okm.check(lib.okm_reader_next(r, 256 << 20, ctypes.byref(seq), ctypes.byref(off), ctypes.byref(nrec)),
+                      "okm_reader_next")
+            if nrec.value == 0:
+                break
+            okm.check(lib.okm_add_batch(c.ctx, seq, off, nrec.value, 1), "okm_add_batch")
+        d = c.count()
+        t2 = time.perf_counter()
+        lib.okm_reader_close(r)
+        return d, {"a_open_ms": 1e3 * (t1 - t0), "a_feed_ms": 1e3 * (t2 - t1)}
+
+    def path_b(c, name="b_ms"):
+        t0 = time.perf_counter()
+        okm.check(lib.okm_add_text(c.ctx, text, n, ctypes.byref(nrec)), "okm_add_text")
+        d = c.count()
+        assert nrec.value == READS
+        return d, {name: 1e3 * (time.perf_counter() - t0)}
+
+    def path_c(c):
+        t0 = time.perf_counter()
+        okm.check(lib.okm_add_text_device(c.ctx, dbuf.ptr, n, ctypes.byref(nrec)), "okm_add_text_device")
+        d = c.count()
+        assert nrec.value == READS
+        return d, {"c_ms": 1e3 * (time.perf_counter() - t0)}
+
+    reps, tables = [], set()
+    with okm.KmerCounter(k) as c:
+        def once(fn, *a):
+            c.reset()
+            d, r = fn(c, *a)
+            tables.add((d, c.engine_info()["kmers"]))
+            return r
+
+        for fn in (path_a, path_b, path_c):  # warm-up: code objects, pinned and device pools
+            once(fn)
+        for _ in range(steps):
+            r = {}
+            for fn in (path_a, path_b, path_c):
+                r.update(once(fn))
+            reps.append(r)
+            log(json.dumps(r))
+        chunks = {}
+        for mib in (16, 64, 256):
+            with testing.knobs(depth_chunk=mib << 20):
+                once(path_b)
+                chunks[f"{mib}MiB"] = round(sorted(once(path_b, "ms")["ms"] for _ in range(3))[1], 2)
+        c.reset()
+        c.set_timing(True)
+        path_c(c)
+        kernels = {name: round(v["total_ms"], 4) for name, v in c.kernel_stats().items()
+                   if name.startswith("text_")}
+        c.set_timing(False)
+    assert len(tables) == 1, f"the paths' tables differ: {tables}"
+    dbuf.free()
+    os.unlink(tmp.name)
+
+    def med(name):
+        return sorted(r[name] for r in reps)[len(reps) // 2]
+
+    a_feed, a_open, b, cc = med("a_feed_ms"), med("a_open_ms"), med("b_ms"), med("c_ms")
+    out = {"metric": "1 GiB of configs[1] FASTQ text in host memory to the counted table (k=31) on one MI355X: "
+                     "okm_add_text + okm_count, host wall ms, median", "value": round(b, 2), "unit": "ms",
+           "n_gpus": 1, "steps": steps, "warmup": 1, "higher_is_better": False,
+           "data": "synthetic (BASELINE configs[1] reads as 320-byte FASTQ records)",
+           "config": {"workload": "add_text: reader batches + okm_add_batch (a), okm_add_text (b), "
+                                  "okm_add_text_device (c), each with okm_count, alternated in one process",
+                      "k": k, "text_bytes": n, "records": READS, "distinct": next(iter(tables))[0],
+                      "kmers": next(iter(tables))[1]},
+           "a_feed_ms": round(a_feed, 2), "a_open_ms": round(a_open, 2), "b_ms": round(b, 2), "c_ms": round(cc, 2),
+           "b_over_a_feed": round(b / a_feed, 4), "b_over_a_with_open": round(b / (a_feed + a_open), 4),
+           "b_ms_by_chunk": chunks, "text_kernels_ms_one_pass": kernels, "repeats": reps}
+    with open(os.path.join(ROOT, "profiles", "add_text.jsonl"), "a") as f:
+        f.write(json.dumps(out) + "\n")
+    return out
+
+
 def ont_batch(gbases: float, seed: int = 4):
     """ONT-like reads (okm.workloads.c4_reads): lognormal
     lengths (median 2,891, sigma 1.085, 200..100k), either strand, 5 %
@@ -1574,7 +1703,7 @@ def wl_classify(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth", "compare", "compare_histogram", "combine", "solid_runs", "count_quantiles", "count_intervals"],
+    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth", "compare", "compare_histogram", "combine", "solid_runs", "count_quantiles", "count_intervals", "add_text"],
                     required=True)
     ap.add_argument("--no-ref", action="store_true", help="c3: skip the one-GPU reference table")
     ap.add_argument("--c3-reads", type=int, default=C3_READS,
@@ -1600,7 +1729,7 @@ def main():
     out = {"query": wl_query, "build": wl_build, "wide": wl_wide, "classify": wl_classify,
            "c5": c5, "c3": wl_c3_loop, "histogram": wl_histogram, "lookup": wl_lookup, "depth": wl_depth,
            "compare": wl_compare, "compare_histogram": wl_compare_histogram, "combine": wl_combine, "solid_runs": wl_solid_runs, "count_quantiles": wl_count_quantiles,
-           "count_intervals": wl_count_intervals}[args.workload](args)
+           "count_intervals": wl_count_intervals, "add_text": wl_add_text}[args.workload](args)
     if out is not None:
         print(json.dumps(out), flush=True)
 

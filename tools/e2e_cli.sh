@@ -18,10 +18,15 @@ run() {
 cat "$D/c2.fastq" > /dev/null
 # five plain runs (the first to a fresh file, then over it): the box's I/O
 # and CPU share vary run to run, so the median is the number to quote
+# (each followed by the same run with --device-parse: the text parsed on the
+# GPU, alternated so that both see the same box)
 for i in 1 2 3 4 5; do
     OKM_PROFILE_HOST=1 run count -k 31 -i "$D/c2.fastq" -o "$D/out.tsv" 2>&1 | tee -a "$D/plain.txt"
+    OKM_PROFILE_HOST=1 run count -k 31 -i "$D/c2.fastq" -o "$D/out_dp.tsv" --device-parse 2>&1 | tee -a "$D/dparse.txt"
 done
 python3 -c "import re,statistics,sys; v=[float(x) for x in re.findall(r'e2e ([0-9.]+) s', open(sys.argv[1]).read())]; print('plain runs', v, 'median', statistics.median(v), 'best', min(v))" "$D/plain.txt"
+python3 -c "import re,statistics,sys; v=[float(x) for x in re.findall(r'e2e ([0-9.]+) s', open(sys.argv[1]).read())]; print('device-parse runs', v, 'median', statistics.median(v), 'best', min(v))" "$D/dparse.txt"
+cmp "$D/out.tsv" "$D/out_dp.tsv" && echo "device-parse table identical"
 OKM_PROFILE_HOST=1 run count -k 31 -i "$D/c2.fastq" -o "$D/out2.tsv" -m 2
 run count -k 31 -i "$D/c2.fastq.gz" -o "$D/out.tsv.gz"
 # the two halves of that run apart: gzip input to a plain table (three runs with
