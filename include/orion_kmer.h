@@ -492,6 +492,43 @@ typedef enum okm_combine_op {
 okm_status okm_combine_counts(okm_ctx *a, okm_ctx *b, okm_combine_op op, uint64_t min_count_a, uint64_t min_count_b,
                               okm_ctx *out, uint64_t *n_out /* may be NULL */);
 
+/* The co-occurrence matrix of a membership table; an extension.  Counts add as
+ * u64 weights, so when sample i adds each of its keys once with weight 1 << i
+ * (okm_add_pairs*, okm_add_sorted_pairs_device), the counted table is the union
+ * of the samples and every entry's count is its membership mask (a sum of
+ * distinct powers of two is their OR and cannot overflow).  With m the low
+ * n_bits bits of an entry's count, 1 <= n_bits <= 64 (higher bits are ignored):
+ *   matrix[i * n_bits + j] = entries whose m has bits i and j   (symmetric; the
+ *                            diagonal holds the samples' sizes)
+ *   occupancy[p]           = entries whose m has exactly p bits, p = 0..n_bits
+ *                            (core, accessory, singletons; the sum is the table's entries)
+ * From the matrix follow Jaccard (M[i][j] / (M[i][i] + M[j][j] - M[i][j])),
+ * containment, Mash distance and a clustering.  Counts first if batches are
+ * pending; an empty table gives zeros.  Read-only, like okm_count_histogram:
+ * only the counts are read, in one pass, where and as the table lies.  n_bits
+ * outside 1..64 or a null ctx / matrix: OKM_E_ARG.  A set-mode context has no
+ * counts: OKM_E_STATE. */
+okm_status okm_count_mask_matrix(okm_ctx *ctx, uint32_t n_bits, uint64_t *matrix /* host, n_bits * n_bits, row-major */,
+                                 uint64_t *occupancy /* host, n_bits + 1; may be NULL */);
+
+/* All-against-all shared k-mers of up to 64 samples in one pass, instead of
+ * n (n - 1) / 2 calls of okm_compare_counts: matrix[i * n + j] = keys kept in
+ * samples[i] and in samples[j], occupancy[p] = keys kept in exactly p samples
+ * (occupancy[0] = 0).  A key is kept when its count is at least min_count (0
+ * behaves as 1); a set-mode sample keeps all its keys.  Set-mode and count-mode
+ * samples mix; the same context may appear more than once; an empty sample
+ * gives a zero row and column.  The samples are counted first if batches are
+ * pending and gathered as okm_fetch_counts gathers them; their tables are not
+ * changed.  LIMIT: 1 <= n <= 64 samples per call (one bit of a u64 count
+ * each); more need several calls over subsets.  FOOTPRINT: the kept keys of
+ * ALL samples and one u64 weight per kept key (16 B per kept key, 24 B for k >
+ * 32) are held on the device at once, beside the union table being counted
+ * from them (an internal context, destroyed before the call returns).  No
+ * memory for that: OKM_E_NOMEM, every sample as it was.  n == 0, n > 64, a null
+ * pointer, or samples of different k, width or device: OKM_E_ARG. */
+okm_status okm_pairwise_shared(okm_ctx *const *samples, uint32_t n, uint64_t min_count,
+                               uint64_t *matrix /* host, n * n */, uint64_t *occupancy /* host, n + 1; may be NULL */);
+
 /* Device pointers to the counted, sorted, unfiltered table (valid until the
  * next add/reset/destroy). */
 okm_status okm_result_device(okm_ctx *ctx, const uint64_t **d_keys, const uint64_t **d_counts,

@@ -224,7 +224,7 @@ static void print_help(const std::string &cmd) {
     else if (cmd == "build")
         printf("Build a unique k-mer database from genome assemblies\n\nUsage: orion-kmer build [OPTIONS] --kmer-size <KMER_SIZE> --genomes <GENOME_FILES>... --output-file <OUTPUT_FILE>\n");
     else if (cmd == "compare")
-        printf("Compare two k-mer databases\n\nUsage: orion-kmer compare [OPTIONS] --db1 <DB1> --db2 <DB2> --output-file <OUTPUT_FILE>\n");
+        printf("Compare two k-mer databases\n\nUsage: orion-kmer compare [OPTIONS] --db1 <DB1> --db2 <DB2> --output-file <OUTPUT_FILE>\n\nOptions:\n      --pairwise-output <FILE>  Also write the shared k-mers of every pair of references of both databases (at most 64 in all): name_i<TAB>name_j<TAB>kmers_i<TAB>kmers_j<TAB>shared<TAB>jaccard (extension)\n");
     else if (cmd == "query")
         printf("Query short reads against a k-mer database\n\nUsage: orion-kmer query [OPTIONS] --database <DATABASE_FILE> --reads <READS_FILE> --output-file <OUTPUT_FILE>\n\nOptions:\n  -d, --database <DATABASE_FILE>  K-mer database to query against. Supports .gz, .xz, .zst compression.\n  -r, --reads <READS_FILE>        Short-read file (FASTQ). Supports .gz, .xz, .zst compression.\n  -o, --output-file <OUTPUT_FILE>  Output file for the IDs of matching reads. Supports .gz, .xz, .zst compression based on extension.\n  -c, --min-hits <MIN_HITS>       Minimum number of k-mer hits to report a read [default: 1]\n  -h, --help                      Print help\n");
     else if (cmd == "classify")
@@ -1037,9 +1037,50 @@ static int unify(const okm_db *db, std::vector<uint64_t> &out) {
     return 0;
 }
 
+// --pairwise-output: every reference of db1, then of db2, is one sample (a SET
+// context of its keys); okm_pairwise_shared gives the shared k-mers of all
+// pairs in one pass, written as one line per unordered pair i < j:
+// name_i<TAB>name_j<TAB>kmers_i<TAB>kmers_j<TAB>shared<TAB>jaccard.
+static int write_pairwise(const okm_db *d1, const okm_db *d2, const std::string &out_path) {
+    const uint64_t n1 = okm_db_num_references(d1), n = n1 + okm_db_num_references(d2);
+    if (n > 64)
+        return die("--pairwise-output takes at most 64 references in all (one bit of a 64-bit membership mask each); "
+                   "the two databases hold " + std::to_string(n));
+    std::string lines;
+    if (n) {
+        std::vector<CompareCtx> samples(n);
+        std::vector<okm_ctx *> ctxs(n);
+        std::vector<const char *> names(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint64_t *keys;
+            uint64_t nk;
+            okm_db_reference(i < n1 ? d1 : d2, i < n1 ? i : i - n1, &names[i], &keys, &nk);
+            if (int rc = open_engine(&samples[i].c, okm_db_k(d1), OKM_MODE_SET)) return rc;
+            if (nk && okm_add_pairs(samples[i].c, keys, nullptr, nk) != OKM_OK)
+                return die("GPU engine failure while comparing: " + err_detail());
+            ctxs[i] = samples[i].c;
+        }
+        std::vector<uint64_t> m(n * n);
+        if (okm_pairwise_shared(ctxs.data(), (uint32_t)n, 1, m.data(), nullptr) != OKM_OK)
+            return die("GPU engine failure while comparing all pairs: " + err_detail());
+        char buf[32];
+        for (uint64_t i = 0; i < n; ++i)
+            for (uint64_t j = i + 1; j < n; ++j) {
+                const uint64_t ki = m[i * n + i], kj = m[j * n + j], sh = m[i * n + j], uni = ki + kj - sh;
+                snprintf(buf, sizeof(buf), "%.6f", uni ? (double)sh / (double)uni : 0.0);
+                lines += std::string(names[i]) + '\t' + names[j] + '\t' + std::to_string(ki) + '\t' + std::to_string(kj) +
+                         '\t' + std::to_string(sh) + '\t' + buf + '\n';
+            }
+    }
+    if (okm_write_file(out_path.c_str(), reinterpret_cast<const uint8_t *>(lines.data()), lines.size()) != OKM_OK)
+        return die("Failed to get output writer for pairwise output file: " + dbg_path(out_path));
+    return 0;
+}
+
 // compare.rs:29-97
 static int run_compare(const Args &a) {
-    std::string p1, p2, out;
+    std::string p1, p2, out, pairwise;
+    get_one(a, "pairwise-output", pairwise);
     if (!get_one(a, "db1", p1)) return usage_error("the following required arguments were not provided:\n  --db1 <DB1>");
     if (!get_one(a, "db2", p2)) return usage_error("the following required arguments were not provided:\n  --db2 <DB2>");
     if (!get_one(a, "output-file", out)) return usage_error("the following required arguments were not provided:\n  --output-file <OUTPUT_FILE>");
@@ -1063,8 +1104,8 @@ static int run_compare(const Args &a) {
         return die("K-mer databases have incompatible k-mer sizes (overall comparison): " + std::to_string(k1) + " vs " + std::to_string(k2));
     }
     std::vector<uint64_t> A, B;
-    int rc;
-    if ((rc = unify(d1, A)) || (rc = unify(d2, B))) {
+    int rc = pairwise.empty() ? 0 : write_pairwise(d1, d2, pairwise);
+    if (rc || (rc = unify(d1, A)) || (rc = unify(d2, B))) {
         okm_db_free(d1);
         okm_db_free(d2);
         return rc;
@@ -1471,6 +1512,7 @@ int main(int argc, char **argv) {
         spec.push_back({"db1", 0, true, false});
         spec.push_back({"db2", 0, true, false});
         spec.push_back({"output-file", 'o', true, false});
+        spec.push_back({"pairwise-output", 0, true, false});
     } else if (cmd == "help") {
         print_help(ci + 1 < argc ? argv[ci + 1] : "");
         return 0;

@@ -3895,6 +3895,105 @@ okm_status okm_count_histogram(okm_ctx *c, uint64_t *hist, uint64_t n_bins, okm_
     return OKM_OK;
 }
 
+// The co-occurrence matrix of a membership table (okm_cooccur.hip): the
+// histogram's walk over the counts alone (TableForm::Counts), each count read
+// as a mask.  The device result is the matrix and then the occupancy.
+okm_status okm_count_mask_matrix(okm_ctx *c, uint32_t n_bits, uint64_t *matrix, uint64_t *occupancy) {
+    if (!c || !matrix) return fail(OKM_E_ARG, "okm_count_mask_matrix: null argument");
+    if (n_bits < 1 || n_bits > 64)
+        return fail(OKM_E_ARG, "okm_count_mask_matrix: n_bits " + std::to_string(n_bits) + " is not in 1..=64");
+    if (c->mode == OKM_MODE_SET) return fail(OKM_E_STATE, "okm_count_mask_matrix: a set-mode context has no counts");
+    HIP_TRY(hipSetDevice(c->device));
+    OKM_TRY(okm_count(c, nullptr));
+    const size_t cells = (size_t)n_bits * n_bits, words = cells + n_bits + 1;
+    memset(matrix, 0, cells * sizeof(uint64_t));
+    if (occupancy) memset(occupancy, 0, (n_bits + 1) * sizeof(uint64_t));
+    if (c->n_res == 0) return OKM_OK;
+    unsigned long long *dm = nullptr;
+    uint32_t *part = nullptr;
+    Blocks scratch(*c->pool);
+    OKM_TRY(scratch.get(words, &dm));
+    OKM_TRY(scratch.get(mask_matrix_part_words(), &part));
+    HIP_TRY(hipMemsetAsync(dm, 0, words * sizeof(unsigned long long), c->stream));
+    TableReader tab(c, TableForm::Counts);
+    OKM_TRY(tab.prepare(scratch));
+    for (uint64_t si = 0; si < tab.nslices; ++si) {
+        OKM_TRY(tab.upload(c->stream, si));
+        const TableView v = tab.view(si);
+        c->timer.begin(c->stream);
+        if (tab.pending)
+            launch_mask_matrix_items(c->stream, c->pend.items, c->pend.nitems, c->pend.n_out, v.counts, v.narrow, n_bits,
+                                     part, dm);
+        else
+            launch_mask_matrix_dense(c->stream, v.counts, v.n, n_bits, part, dm);
+        c->timer.end(c->stream, "mask_matrix", (v.narrow ? 4.0 : 8.0) * (double)v.n);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(matrix, dm, cells * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (occupancy)
+        HIP_TRY(hipMemcpyAsync(occupancy, dm + cells, (n_bits + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    OKM_TRY(sync(c));
+    scratch.free_all();
+    return OKM_OK;
+}
+
+// All-against-all shared keys of up to 64 samples: sample i's kept keys go,
+// sorted as its table holds them, into a scratch context of the same k and
+// width with weight 1 << i (okm_add_sorted_pairs_device: the runs are merged,
+// not partitioned; the count itself falls back to partitioning where a plan
+// of sorted runs does not fit).  The weights of one key are distinct powers of
+// two, so their sum is their OR: the counted union's counts are the membership
+// masks, and okm_count_mask_matrix reads them.  The copies (every sample's
+// kept keys and as many weights) live in the scratch context's pool until it
+// is counted; a sample is counted and gathered as okm_fetch_counts does it and
+// is otherwise left alone.
+okm_status okm_pairwise_shared(okm_ctx *const *samples, uint32_t n, uint64_t min_count, uint64_t *matrix,
+                               uint64_t *occupancy) {
+    if (!samples || !matrix) return fail(OKM_E_ARG, "okm_pairwise_shared: null argument");
+    if (n < 1 || n > 64) return fail(OKM_E_ARG, "okm_pairwise_shared: " + std::to_string(n) + " samples; one call takes 1..=64");
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!samples[i]) return fail(OKM_E_ARG, "okm_pairwise_shared: null sample");
+        if (samples[i]->k != samples[0]->k || samples[i]->wide != samples[0]->wide)
+            return fail(OKM_E_ARG, "okm_pairwise_shared: the samples differ in k or in key width");
+        if (samples[i]->device != samples[0]->device)
+            return fail(OKM_E_ARG, "okm_pairwise_shared: the samples are on different devices");
+    }
+    min_count = std::max<uint64_t>(min_count, 1);
+    okm_ctx *first = samples[0], *u = nullptr;
+    HIP_TRY(hipSetDevice(first->device));
+    std::vector<uint64_t> kept(n);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) {  // (counts a pending sample; a set-mode sample keeps every key)
+        OKM_TRY(okm_result_size(samples[i], samples[i]->mode == OKM_MODE_SET ? 1 : min_count, &kept[i]));
+        total += kept[i];
+    }
+    OKM_TRY(okm_create(&u, first->k, (okm_mode)(OKM_MODE_COUNT | (first->wide ? OKM_MODE_WIDE : 0)), first->device, total));
+    okm_status st = OKM_OK;
+    {
+        Blocks copies(*u->pool);
+        for (uint32_t i = 0; i < n && st == OKM_OK; ++i) {
+            if (!kept[i]) continue;
+            okm_ctx *s = samples[i];
+            uint64_t *dk = nullptr, *dw = nullptr, got = 0;
+            if (copies.get(kept[i] * s->kw, &dk) != OKM_OK || copies.get(kept[i], &dw) != OKM_OK) {
+                st = fail(OKM_E_NOMEM, "okm_pairwise_shared: no device memory for the copies of " + std::to_string(total) +
+                                           " kept keys and their weights");
+                break;
+            }
+            // (the copy runs on the sample's stream and is complete when the call returns)
+            st = okm_fetch_counts(s, s->mode == OKM_MODE_SET ? 1 : min_count, dk, nullptr, kept[i], &got, 1);
+            if (st != OKM_OK) break;
+            launch_fill_weight(u->stream, dw, got, 1ull << i);
+            st = okm_add_sorted_pairs_device(u, dk, dw, got);
+        }
+        if (st == OKM_OK) st = okm_count(u, nullptr);  // (the borrowed runs are released once counted)
+        copies.free_all();
+    }
+    if (st == OKM_OK) st = okm_count_mask_matrix(u, n, matrix, occupancy);
+    okm_destroy(u);
+    return st;
+}
+
 // The counts of given keys, searched in the table (TableForm::Search).  Every
 // slice of a host-resident table is searched for all queries and writes only
 // the queries it finds.  Host queries go through scratch in chunks of

@@ -327,6 +327,21 @@ void launch_hist_items(void *stream, const DevItem *items, uint32_t nitems, cons
 void launch_hist_dense(void *stream, const uint64_t *counts, uint64_t n, uint64_t min_count, uint64_t n_bins,
                        unsigned long long *hist, unsigned long long *summary);
 
+// Co-occurrence matrix of a membership table (okm_cooccur.hip): every count is
+// a mask of n_bits bits (1..64; higher bits ignored), out[i * n_bits + j] +=
+// entries whose mask has bits i and j, out[n_bits * n_bits + p] += entries with
+// p bits set.  out (zeroed by the caller) takes any number of launches.  The
+// two forms read what launch_hist_items / launch_hist_dense read.  part:
+// mask_matrix_part_words() u32 words of scratch, the workgroups' partials.
+size_t mask_matrix_part_words();
+void launch_mask_matrix_items(void *stream, const DevItem *items, uint32_t nitems, const unsigned long long *n_out,
+                              const uint64_t *counts, bool narrow, uint32_t n_bits, uint32_t *part,
+                              unsigned long long *out);
+void launch_mask_matrix_dense(void *stream, const uint64_t *counts, uint64_t n, uint32_t n_bits, uint32_t *part,
+                              unsigned long long *out);
+// w[0, n) = weight (okm_pairwise_shared: sample i's membership bit beside its keys).
+void launch_fill_weight(void *stream, uint64_t *w, uint64_t n, uint64_t weight);
+
 // A counted table as the in-place readers' kernels see it (the lookup, the
 // depth, the compare): one of two forms, both sorted by key.  The host's
 // TableReader (okm_engine.hip) fills it for the representation the table lies

@@ -417,6 +417,19 @@ class KmerCounter:
               "okm_count_histogram")
         return hist, {f: int(getattr(sm, f)) for f, _ in _lib.CountSummary._fields_}
 
+    def mask_matrix(self, n_bits: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Every count read as a membership mask of n_bits bits (1..64): the
+        uint64 matrix M[i, j] = entries whose mask has bits i and j, and
+        occupancy[p] = entries with exactly p bits set, p = 0..n_bits; read
+        from the table where it lies (okm_count_mask_matrix)."""
+        nb = int(n_bits)
+        ok = 1 <= nb <= 64  # (the library refuses the rest: nothing is allocated for it)
+        m = np.zeros((nb, nb) if ok else (1, 1), dtype=np.uint64)
+        occ = np.zeros(nb + 1 if ok else 1, dtype=np.uint64)
+        check(lib().okm_count_mask_matrix(self.ctx, nb & (2 ** 32 - 1), m.ctypes.data, occ.ctypes.data),
+              "okm_count_mask_matrix")
+        return m, occ
+
     def lookup(self, keys: np.ndarray) -> np.ndarray:
         """counts[i] = the count of canonical key i, 0 when it is absent; the
         table is searched where it lies (okm_lookup_counts).  Wide contexts
@@ -759,6 +772,21 @@ def distributed_compare(comm: "Comm", a: "KmerCounter", b: "KmerCounter", owner_
         inter = set_intersection_size_device(pa, na, pb, nb, owner_a.device)
     ta, tb, ti = comm.allreduce([na, nb, inter])
     return ta, tb, ti
+
+
+def pairwise_shared(counters: Sequence["KmerCounter"], min_count: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+    """All-against-all shared keys of 1..64 counters of one k, width and device
+    in one pass (okm_pairwise_shared): the uint64 matrix M[i, j] = keys kept
+    (count >= min_count; a set-mode counter keeps all) in counters i and j, and
+    occupancy[p] = keys kept in exactly p of them.  Jaccard(i, j) = M[i, j] /
+    (M[i, i] + M[j, j] - M[i, j])."""
+    n = len(counters)
+    ok = 1 <= n <= 64  # (the library refuses the rest: nothing is allocated for it)
+    m = np.zeros((n, n) if ok else (1, 1), dtype=np.uint64)
+    occ = np.zeros(n + 1 if ok else 1, dtype=np.uint64)
+    ctxs = (c_void_p * max(n, 1))(*[c.ctx.value for c in counters])
+    check(lib().okm_pairwise_shared(ctxs, n, min_count, m.ctypes.data, occ.ctypes.data), "okm_pairwise_shared")
+    return m, occ
 
 
 def set_intersection_size(a: np.ndarray, b: np.ndarray, device: int = 0) -> int:

@@ -191,6 +191,8 @@ PROTOTYPES = {
     "okm_count_histogram": (c_int, [c_void_p, c_void_p, c_uint64, POINTER(CountSummary)]),
     "okm_group_count_histogram": (c_int, [c_void_p, c_void_p, c_uint64, POINTER(CountSummary)]),
     "okm_write_histogram_tsv": (c_int, [c_char_p, c_void_p, c_uint64]),
+    "okm_count_mask_matrix": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p]),
+    "okm_pairwise_shared": (c_int, [POINTER(c_void_p), c_uint32, c_uint64, c_void_p, c_void_p]),
     "okm_lookup_counts": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_int, _P64]),
     "okm_group_lookup_counts": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, _P64]),
     "okm_compare_counts": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, POINTER(CountCompare)]),

@@ -79,6 +79,13 @@ input, warmup then timed steps bracketed by device syncs).
                      okm_add_text_device on resident text; the text kernels'
                      HIP-event times and okm_add_text at other chunk sizes; the
                      line is appended to profiles/add_text.jsonl.
+  --workload pairwise okm_count_mask_matrix at 8 and 64 bits beside
+                     okm_count_histogram on the configs[1] table (pending, then
+                     dense), and okm_pairwise_shared of 8 and 64 groups of its
+                     reads beside the n(n-1)/2 okm_compare_counts calls it
+                     replaces, equal matrices asserted (--table-only: the
+                     first part alone, for A/B builds); the line is appended
+                     to profiles/pairwise.jsonl.
 
 The CPU baseline is the C restatement (oracle/) on a bounded sample, 1 thread.
 """
@@ -249,6 +256,96 @@ def wl_histogram(args):
             "roofline": {"bound": "hbm", "kernel": "k_hist_items<narrow>", "alg_bytes_per_step": alg,
                          "achieved": round(alg / (h_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(alg / (h_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}}
+
+
+def wl_pairwise(args):
+    """(a) okm_count_mask_matrix at 8 and 64 bits beside okm_count_histogram on
+    the C2 table, pending and then dense, the three alternated call by call
+    (HIP-event ms per call from kernel_stats(), medians of --steps).  The
+    table's counts stand in for masks: the kernel's work does not depend on
+    their values, only the occupancy bins they hit.  (b) okm_pairwise_shared
+    over 8 and 64 samples cut from the C2 reads, alternated run by run with the
+    composition it replaces, n (n - 1) / 2 okm_compare_counts calls (host wall
+    ms, medians of --steps), the two matrices asserted equal.  The line is
+    appended to profiles/pairwise.jsonl."""
+    k = 31
+    batch = c2_batch()
+    dbuf = okm.DeviceBuffer(len(batch))
+    dbuf.upload(batch)
+
+    def med(v):
+        v = sorted(v)
+        return {"median": round(v[len(v) // 2], 4), "min": round(v[0], 4), "max": round(v[-1], 4)}
+
+    table = {}
+    with okm.KmerCounter(k) as c:
+        c.add_device_batch(dbuf.address, len(batch))
+        distinct = c.count()
+        c.set_timing(True)
+        calls = {"mask_matrix_8": ("mask_matrix", lambda: c.mask_matrix(8)),
+                 "mask_matrix_64": ("mask_matrix", lambda: c.mask_matrix(64)),
+                 "count_histogram": ("count_histogram", lambda: c.count_histogram(10001))}
+        for form in ("pending", "dense"):
+            if form == "dense":
+                c.result_device()
+            ms = {name: [] for name in calls}
+            for it in range(args.warmup + args.steps):
+                for name, (kernel, fn) in calls.items():
+                    before = c.kernel_stats().get(kernel, {"total_ms": 0.0, "alg_bytes": 0.0})
+                    fn()
+                    after = c.kernel_stats()[kernel]
+                    if it >= args.warmup:
+                        ms[name].append(after["total_ms"] - before["total_ms"])
+                    alg = after["alg_bytes"] - before["alg_bytes"]
+            row = {name: med(v) for name, v in ms.items()}
+            h = row["count_histogram"]["median"]
+            row.update(alg_bytes_per_call=alg, over_count_histogram={n: round(row[n]["median"] / h, 4) for n in ms if n != "count_histogram"},
+                       gbs={n: round(alg / (row[n]["median"] * 1e-3) / 1e9, 1) for n in ms})
+            table[form] = row
+        assert int(c.mask_matrix(64)[1].sum()) == distinct
+    shared = {}
+    for n in () if args.table_only else (8, 64):
+        per = (READS // n) * (READ_LEN + 1)
+        counters = [okm.KmerCounter(k) for _ in range(n)]
+        for i, s in enumerate(counters):
+            s.add_device_batch(dbuf.address + i * per, per)
+            s.count()
+
+        def composed():
+            m = np.zeros((n, n), np.uint64)
+            for i in range(n):
+                for j in range(i + 1, n):
+                    cc = counters[i].compare_counts(counters[j])
+                    m[i, j] = m[j, i] = cc["n_shared"]
+                    m[i, i], m[j, j] = cc["n_a"], cc["n_b"]
+            return m
+
+        one, many = [], []
+        for it in range(1 + args.steps):  # (one warm-up of each)
+            t = time.perf_counter()
+            m, occ = okm.pairwise_shared(counters)
+            t1 = time.perf_counter()
+            ref = composed() if n > 1 else m
+            t2 = time.perf_counter()
+            assert np.array_equal(m, ref), "pairwise_shared != the compare_counts composition"
+            if it:
+                one.append((t1 - t) * 1e3)
+                many.append((t2 - t1) * 1e3)
+        shared[f"n{n}"] = {"pairwise_shared_wall_ms": med(one), "composition_wall_ms": med(many), "compare_calls": n * (n - 1) // 2,
+                           "pairwise_over_composition": round(med(one)["median"] / med(many)["median"], 4),
+                           "kept_keys": int(np.trace(m)), "union": int(occ.sum()), "core": int(occ[n])}
+        for s in counters:
+            s.close()
+    dbuf.free()
+    return {"metric": "co-occurrence matrix at 64 bits of the pending C2 table (k=31) on one MI355X, HIP-event ms",
+            "value": table["pending"]["mask_matrix_64"]["median"], "unit": "ms", "n_gpus": 1, "steps": args.steps,
+            "warmup": args.warmup, "higher_is_better": False, "dtype": "u32 / u64 counts as masks, u32 registers and LDS, u64 matrix",
+            "data": "synthetic (BASELINE configs[1] reads, device-resident)",
+            "config": {"workload": "pairwise: 3,355,443 x 150 bp reads counted; mask_matrix beside count_histogram; "
+                                   "pairwise_shared of 8 and 64 read groups beside n(n-1)/2 compare_counts", "k": k,
+                       "distinct": int(distinct),
+                       "lib": os.path.basename(os.path.dirname(os.environ.get("OKM_LIB", ""))) or "build"},
+            "mask_matrix": table, "pairwise_shared": shared}
 
 
 class _DevView:
@@ -1703,7 +1800,7 @@ def wl_classify(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth", "compare", "compare_histogram", "combine", "solid_runs", "count_quantiles", "count_intervals", "add_text"],
+    ap.add_argument("--workload", choices=["query", "build", "wide", "classify", "c5", "c3", "histogram", "lookup", "depth", "compare", "compare_histogram", "combine", "solid_runs", "count_quantiles", "count_intervals", "add_text", "pairwise"],
                     required=True)
     ap.add_argument("--no-ref", action="store_true", help="c3: skip the one-GPU reference table")
     ap.add_argument("--c3-reads", type=int, default=C3_READS,
@@ -1717,6 +1814,7 @@ def main():
     ap.add_argument("--cpu-sample-reads", type=int, default=100_000)
     ap.add_argument("--loopback", type=int, default=0,
                     help="c5: P virtual ranks on one GPU through okm_comm_init_loopback (the distributed compare)")
+    ap.add_argument("--table-only", action="store_true", help="pairwise: part (a) alone (A/B builds of the kernel)")
     ap.add_argument("--knob", action="append", default=[],
                     help="NAME=VALUE: an engine test knob for the run (okm.testing; A/B of rare paths)")
     args = ap.parse_args()
@@ -1729,7 +1827,7 @@ def main():
     out = {"query": wl_query, "build": wl_build, "wide": wl_wide, "classify": wl_classify,
            "c5": c5, "c3": wl_c3_loop, "histogram": wl_histogram, "lookup": wl_lookup, "depth": wl_depth,
            "compare": wl_compare, "compare_histogram": wl_compare_histogram, "combine": wl_combine, "solid_runs": wl_solid_runs, "count_quantiles": wl_count_quantiles,
-           "count_intervals": wl_count_intervals, "add_text": wl_add_text}[args.workload](args)
+           "count_intervals": wl_count_intervals, "add_text": wl_add_text, "pairwise": wl_pairwise}[args.workload](args)
     if out is not None:
         print(json.dumps(out), flush=True)
 
